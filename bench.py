@@ -1,6 +1,6 @@
 """bench.py — keystep-samples/sec (train fwd+bwd) of the 3D-LOTUS v1 policy on N MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
 
 N > 1: one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process is
 one rank; started bare, `--gpus N` re-executes itself through `python -m torch.distributed.run --nproc-per-node N`
@@ -193,6 +193,35 @@ def self_launch(n):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_SAMPLE = 1 << 21  # --dump-outputs: entries kept of a larger output (8 MB of float32 per array)
+
+
+def dump_outputs(out_dir, losses, model, params):
+    """--dump-outputs: what the last timed step handed its caller — the losses and the parameter gradients — and the head
+    predictions it left in model.last_pred, as out_dir/<name>.npy (float64 losses and gradient norms, float32 otherwise).
+    An output of more than DUMP_SAMPLE entries is stored as its entries at DUMP_SAMPLE sorted positions of the flattened
+    array, drawn from a fixed seed: the same positions in every run, so two builds compare entry for entry."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    out = {f"loss_{k}": v.detach().double().cpu().numpy() for k, v in losses.items()}
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    out["grad_norm"] = torch.stack([g.double().norm() for g in grads]).cpu().numpy()  # one per parameter, model.parameters() order
+    big = {"grad": torch.cat([g.reshape(-1) for g in grads])}
+    for name, t in zip(("pred_pos", "pred_rot", "pred_open", "pred_stop"), model.last_pred):
+        big[name] = torch.stack(list(t)) if isinstance(t, (list, tuple)) else t
+    for name, t in big.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        out[name] = t.float().cpu().numpy()
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _watchdog(rank, limit_s):
     """-> tick(what=None).  A daemon thread ends the process (exit code 17, Python stacks of all threads on stderr) when
     `limit_s` seconds pass without a tick."""
@@ -250,8 +279,13 @@ def main():
     ap.add_argument("--no-side-workloads", action="store_true",
                     help="skip the side measurements of the other BASELINE workloads (PerAct bf16 at 16 / 64 clouds, motion planner)")
     ap.add_argument("--gemm-report", default=None, help="write per-shape GEMM timings (diagnostic) to this file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, parameter gradients, head predictions) to "
+                         "DIR/<name>.npy; the inputs are the same in every run with the same arguments")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_only:
         import robot_3dlotus_amd  # noqa: F401
         print(json.dumps(cpu_baseline_measure()), flush=True)
@@ -404,6 +438,8 @@ def main():
     dt = time.perf_counter() - t0
     if step_marks:
         print("step times ms:", " ".join("%.2f" % a.elapsed_time(b) for a, b in zip(step_marks, step_marks[1:])), file=sys.stderr)
+    if args.dump_outputs and rank == 0:  # before any further step() overwrites the gradients
+        dump_outputs(args.dump_outputs, losses, model, params)
     bn_msgs = parallel.BN_MESSAGES - bn_msgs0
     # per-rank communication figures (outside the timed region): GPU time the backward stream waited in finish() per step,
     # GPU time of the SyncBN statistics messages of one extra step, and the point counts the ranks hold

@@ -58,6 +58,17 @@ def zero_dropouts(model):
 
 
 def run_case(name, spec, out_dir=HERE):
+    # one intra-op thread: the float outputs of the reference's CPU backward change with the thread count and, with several
+    # threads, from run to run; single-threaded they are reproducible, so a fixture can be regenerated bit for bit
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        _run_case(name, spec, out_dir)
+    finally:
+        torch.set_num_threads(threads)
+
+
+def _run_case(name, spec, out_dir):
     variant, B, n, ragged, dseed, wseed, wvar, train = spec[:8]
     drop_path = spec[8] if len(spec) > 8 else 0.0
     torch.manual_seed(0)

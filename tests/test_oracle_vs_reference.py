@@ -1,5 +1,6 @@
-"""Live check of the oracle against the imported reference (build container only; skipped on
-the GPU box where /root/reference does not exist)."""
+"""The oracle against the reference: live against the imported reference (tests marked `reference`: build container only,
+skipped where /root/reference does not exist), and against the reference's outputs stored in
+tests/golden/serialization_layout.npz (tests/golden/make_golden_serialization.py) everywhere."""
 import copy
 import os
 import sys
@@ -8,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.reference
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _harness():
@@ -19,6 +20,7 @@ def _harness():
     return rh
 
 
+@pytest.mark.reference
 @pytest.mark.parametrize("variant,wvar,B,n,train", [("tiny", "scaled", 3, 700, True), ("tiny", "init", 2, 300, False),
                                                     ("v1", "scaled", 2, 640, True)])
 def test_losses_and_grads_match_reference(variant, wvar, B, n, train):
@@ -49,6 +51,7 @@ def test_losses_and_grads_match_reference(variant, wvar, B, n, train):
         assert (p.grad - sdg[name].grad).norm().item() <= 1e-4 * p.grad.norm().item() + 1e-6 * gmax, name
 
 
+@pytest.mark.reference
 @pytest.mark.parametrize("variant,B,n,train", [("tiny", 3, 1024, True), ("tinydeep", 2, 1024, True), ("tinyctx", 2, 900, False)])
 def test_oracle_matches_the_reference_own_attention_arithmetic(variant, B, n, train):
     """flash_attn is not installed here, so everywhere else the reference runs over the harness' stand-in for it.  With
@@ -96,6 +99,7 @@ def test_oracle_matches_the_reference_own_attention_arithmetic(variant, B, n, tr
         assert (p.grad - stand_in[name].grad).norm().item() <= 1e-4 * p.grad.norm().item() + 1e-6 * gmax, name
 
 
+@pytest.mark.reference
 @pytest.mark.parametrize("variant", ["mp_tiny", "mp_tinyctx"])
 def test_motion_planner_fixtures_stand_on_the_reference_own_attention_arithmetic(variant):
     """The 3D-LOTUS++ motion planner (motion_planner_ptv3.py) over the same backbone: with `enable_flash=False` the reference runs
@@ -133,54 +137,58 @@ def test_motion_planner_fixtures_stand_on_the_reference_own_attention_arithmetic
         assert (p.grad - other[name].grad).norm().item() <= 1e-4 * p.grad.norm().item() + 1e-6 * gmax, name
 
 
+def _golden_serialization():
+    sys.path.insert(0, GOLDEN)
+    import make_golden_serialization as mgs
+
+    return mgs, np.load(os.path.join(GOLDEN, "serialization_layout.npz"))
+
+
 def test_encode_matches_reference_all_depths():
-    rh = _harness()
-    from genrobo3d.models.PointTransformerV3.serialization import encode as ref_encode
+    """The reference's serialization codes of seeded grids, every depth and order (captured by make_golden_serialization.py)."""
     from oracle import front_end as fe
 
-    rng = np.random.default_rng(0)
-    for depth in (1, 3, 7, 8, 9, 12, 16):
-        g = rng.integers(0, 2 ** depth, size=(3000, 3)).astype(np.int32)
-        b = rng.integers(0, 17, size=3000).astype(np.int64)
+    mgs, gold = _golden_serialization()
+    assert tuple(fe.ORDERS) == mgs.ORDERS
+    for depth, g, b in mgs.encode_inputs():
         for o in fe.ORDERS:
-            r = ref_encode(torch.from_numpy(g), torch.from_numpy(b), depth, o).numpy()
-            np.testing.assert_array_equal(fe.encode(g, b, depth, o), r)
+            np.testing.assert_array_equal(fe.encode(g, b, depth, o), gold[f"encode_{depth}_{o}"])
 
 
 def test_hilbert_roundtrip_through_reference_decoder():
-    """Hilbert codes decode back to coordinates with the reference's own decoder."""
-    rh = _harness()
-    from genrobo3d.models.PointTransformerV3.serialization import decode as ref_decode
+    """Hilbert codes decode back to coordinates with the reference's own decoder (its output on the codes
+    below, captured by make_golden_serialization.py)."""
     from oracle import front_end as fe
 
-    rng = np.random.default_rng(1)
-    g = rng.integers(0, 2 ** 9, size=(2000, 3)).astype(np.int32)
-    b = rng.integers(0, 4, size=2000).astype(np.int64)
-    gc, bb = ref_decode(torch.from_numpy(fe.encode(g, b, 9, "hilbert")), 9, "hilbert")
-    np.testing.assert_array_equal(gc.numpy(), g)
-    np.testing.assert_array_equal(bb.numpy(), b)
+    mgs, gold = _golden_serialization()
+    g, b = mgs.hilbert_inputs()
+    np.testing.assert_array_equal(fe.encode(g, b, 9, "hilbert"), gold["hilbert_code"])
+    np.testing.assert_array_equal(gold["hilbert_decoded_grid"], g)
+    np.testing.assert_array_equal(gold["hilbert_decoded_batch"], b)
 
 
 def test_state_template_matches_reference_layout():
-    """Checkpoint-format contract: 460 entries, same names and shapes."""
-    rh = _harness()
+    """Checkpoint-format contract: 460 entries, same names and shapes as the reference policy's
+    state_dict (captured by make_golden_serialization.py)."""
     import golden_util as gu
     from robot_3dlotus_amd import config as lcfg
 
+    _, gold = _golden_serialization()
     for variant in ("v1", "tiny"):
-        ref, _ = rh.build_reference_policy(variant)
-        rsd = ref.state_dict()
+        rsd = {k: tuple(int(x) for x in s.split(",") if x) for k, s in zip(gold[f"layout_{variant}_names"], gold[f"layout_{variant}_shapes"])}
         t = gu.state_template(lcfg.preset(variant))
         assert set(t) == set(rsd)
         for k in t:
-            assert tuple(t[k].shape) == tuple(rsd[k].shape), k
+            assert tuple(t[k].shape) == rsd[k], k
         if variant == "v1":
             assert len(t) == 460
 
 
+@pytest.mark.reference
 def test_committed_fixture_equals_what_the_generator_writes(tmp_path):
     """The committed fixtures ARE the generator's output: regenerate one case from the imported reference
-    and compare every key bit for bit (the 512-point case: its reductions are below the size where the thread count changes the summation order)."""
+    and compare every key bit for bit (the generator runs the reference on one thread: with several, its CPU backward is not
+    reproducible from run to run)."""
     import os
     import sys
 
