@@ -536,6 +536,31 @@ int lotus_adamw_step(const void* p_ptrs, const void* g_ptrs, const void* m_ptrs,
 /* dst[t][i] = bf16(src[t][i]): creation / refresh of the weight shadows outside an optimiser step (same tables as above) */
 int lotus_shadow_cast(const void* src_ptrs, const void* dst_ptrs, const long* numel, const int* chunks, int nchunks, void* stream);
 
+/* ---- adaptive PDNorm (SimplePolicyPTV3AdaNorm, simple_policy_ptv3.py:160-373; fp32 activations only, no bf16 twin) ------- */
+/* PDNorm(adaptive, decouple = False), PointTransformerV3/model.py:280-303: with [shift | scale] = mod[b] (row b of a [B][mod_ld]
+ * table, shift in columns 0..C-1 and scale in C..2C-1; mod_ld may be the width of a wider slab) and b(i) the cloud of row i given
+ * by the level offsets off[B + 1] (int32, off[0] = 0, off[B] = M):
+ *   LayerNorm site (model.py:624,627,645):           y_i = (LN(x_i) gamma + beta) (1 + scale_b(i)) + shift_b(i)  (+ res_i)
+ *   BatchNorm site (model.py:709,808-809,855; + GELU): y_i = act((xhat_i gamma + beta) (1 + scale_b(i)) + shift_b(i))
+ * Backward: dmod[b] = (dshift_b, dscale_b) rows of a [B][dmod_ld] table, dgamma / dbeta written (not accumulated); the
+ * per-(cloud, column) sums behind them are reduced in fixed order (bit-reproducible).  Workspace: lotus_adanorm_workspace. */
+size_t lotus_adanorm_workspace(int M, int B, int C);
+int lotus_adaln_fwd(const float* x, const float* res, const float* gamma, const float* beta, const float* mod, int mod_ld,
+                    const int* off, int B, float* y, float* mean, float* rstd, int M, int C, float eps, void* stream);
+/* dx = LN'(dy) with the per-row gain gamma (1 + scale_b) (+ add) */
+int lotus_adaln_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                    const float* mod, int mod_ld, const int* off, int B, const float* add, float* dx, float* dgamma, float* dbeta,
+                    float* dmod, int dmod_ld, int M, int C, void* workspace, size_t workspace_bytes, void* stream);
+/* mean / invstd: the BatchNorm statistics (lotus_batchnorm_stats_fused in training, lotus_batchnorm_eval_stats in eval) */
+int lotus_adabn_apply(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const float* mod,
+                      int mod_ld, const int* off, int B, float* y, int M, int C, int act, void* stream);
+/* training = 1: batch statistics (dx carries the mean / variance terms), 0: running statistics */
+int lotus_adabn_bwd(const float* dy, const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                    const float* mod, int mod_ld, const int* off, int B, float* dx, float* dgamma, float* dbeta, float* dmod,
+                    int dmod_ld, int M, int C, int act, int training, void* workspace, size_t workspace_bytes, void* stream);
+/* PDNorm.modulation[0] = nn.SiLU (model.py:276-278): y = SiLU(x), or y = dy SiLU'(x) when dy is given */
+int lotus_ada_silu(const float* x, const float* dy, float* y, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,628 @@
+"""Adaptive PDNorm backbone of SimplePolicyPTV3AdaNorm (genrobo3d/models/simple_policy_ptv3.py:160-373) over the HIP operators.
+
+The point backbone is the Block-only PointTransformerV3 (PointTransformerV3/model.py:864-1100) with every norm wrapped in
+PDNorm(adaptive=True, decouple=False) (model.py:257-303): BatchNorm at the stem, every pooling and both unpooling branches,
+LayerNorm at `cpe.2`, `norm1` and `norm2` of every Block.  Norm j of width C is modulated by one vector per cloud,
+[shift_j | scale_j] = Linear_j(SiLU(c_b)), c_b the instruction (+ pose, + step) context of cloud b.
+
+The autograd nodes below are composed of the library's existing per-launch primitives (sparse convolution, dense layers,
+patch attention, BatchNorm statistics) and the modulated-norm entry points of csrc/adanorm.hip.  All modulation projections
+of a forward pass are one product (ModAllFn; the same idea as ops.KvAllFn for the CABlocks): SiLU(c) [B, 256] against the
+concatenated weights of every PDNorm, and one weight-gradient / one input-gradient product in backward over the d mod slab
+that the norms' backward passes fill in place.  fp32 activation storage only.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._capi import call, query, WS
+from .frontend import FrontEnd, draw_order_perms
+from .ops import ACT_GELU, BN_EPS, BN_MOMENTUM, _fwd, _joined, mix_seed
+from .ptv3 import PointTransformerV3CA, SubMConv3d, _Attn, _MLP, _bn
+
+_WS_SLOT = 6  # workspace slot of the (P, Q) partials (main stream)
+
+
+# ------------------------------------------------------------------------------------ primitives
+def _n_clouds(lvl):
+    return len(lvl.counts)
+
+
+def adaln_fwd(x, g, b, mod, lvl, res=None, eps=1e-5):
+    """(LN(x) g + b) (1 + scale_b) + shift_b (+ res); mod = [B, 2C] (row stride free) of [shift | scale]."""
+    M, C = x.shape
+    y = torch.empty_like(x)
+    mean = torch.empty(M, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+    call("lotus_adaln_fwd", x, res, g, b, mod, mod.stride(0), lvl.off, _n_clouds(lvl), y, mean, rstd, M, C, float(eps))
+    return y, mean, rstd
+
+
+def adaln_bwd(dy, x, mean, rstd, g, b, mod, dmod, lvl, add=None):
+    """-> dx (+ add), dgamma, dbeta; d mod written into `dmod` ([B, 2C] view)."""
+    M, C = x.shape
+    B = _n_clouds(lvl)
+    dx = torch.empty_like(x)
+    dg = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    ws = WS.get(query("lotus_adanorm_workspace", M, B, C), x.device, slot=_WS_SLOT)
+    call("lotus_adaln_bwd", dy, x, mean, rstd, g, b, mod, mod.stride(0), lvl.off, B, add, dx, dg, db, dmod, dmod.stride(0), M, C,
+         ws, ws.numel())
+    return dx, dg, db
+
+
+def adabn_fwd(x, g, b, rmean, rvar, mod, lvl, training, act=ACT_GELU):
+    """act((BN(x) g + b) (1 + scale_b) + shift_b): batch statistics (+ running-average update) in training, running ones in eval."""
+    M, C = x.shape
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    invstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    if training:
+        sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
+        ws = ops._ws(query("lotus_batchnorm_workspace", M, C), x.device)
+        call("lotus_batchnorm_stats_fused", x, sums, mean, invstd, rmean, rvar, M, C, float(BN_EPS), float(BN_MOMENTUM), ws,
+             ws.numel(), ops._bn_counter(x.device))
+    else:
+        call("lotus_batchnorm_eval_stats", rmean, rvar, mean, invstd, C, float(BN_EPS))
+    y = torch.empty_like(x)
+    call("lotus_adabn_apply", x, mean, invstd, g, b, mod, mod.stride(0), lvl.off, _n_clouds(lvl), y, M, C, act)
+    return y, mean, invstd
+
+
+def adabn_bwd(dy, x, mean, invstd, g, b, mod, dmod, lvl, training, act=ACT_GELU):
+    M, C = x.shape
+    B = _n_clouds(lvl)
+    dx = torch.empty_like(x)
+    dg = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    ws = WS.get(query("lotus_adanorm_workspace", M, B, C), x.device, slot=_WS_SLOT)
+    call("lotus_adabn_bwd", dy, x, mean, invstd, g, b, mod, mod.stride(0), lvl.off, B, dx, dg, db, dmod, dmod.stride(0), M, C, act,
+         1 if training else 0, ws, ws.numel())
+    return dx, dg, db
+
+
+def silu(x, dy=None):
+    y = torch.empty_like(x)
+    call("lotus_ada_silu", x, dy, y, x.numel())
+    return y
+
+
+# ------------------------------------------------------------------------------------ modulation bank
+class ModBank:
+    """[shift | scale] of every PDNorm of one forward pass: `mod` [B, sum 2C_j], norm j in columns offs[j] : offs[j] + 2C_j.
+    `dmod` (same shape) collects d mod, each norm's backward writing its own column slice."""
+    __slots__ = ("mod", "dmod", "offs", "widths", "slices")
+
+    def slice(self, j):
+        return self.slices[j]
+
+    def grad_slice(self, j):
+        if self.dmod is None:
+            self.dmod = torch.empty_like(self.mod)
+        return self.dmod[:, self.offs[j]:self.offs[j] + self.widths[j]]
+
+
+class ModAllFn(torch.autograd.Function):
+    """mod_j = Linear_j(SiLU(c)) for every PDNorm j in ONE product: SiLU(c) [B, Cc] x cat(W_j) [sum 2C_j, Cc] (v1: 40 norms,
+    24 064 columns).  The weights stay the modules' own parameters; their concatenation is one copy per step."""
+
+    @_fwd
+    def forward(ctx, context, bank, *wb):
+        ws, bs = wb[0::2], wb[1::2]
+        W = torch.cat(ws, 0)
+        bias = torch.cat(bs, 0)
+        s = silu(context)
+        mod, _ = ops.linear_fwd(s, W, bias)
+        bank.mod, bank.dmod = mod, None
+        bank.widths = [w.shape[0] for w in ws]
+        bank.offs = [0]
+        for w_ in bank.widths[:-1]:
+            bank.offs.append(bank.offs[-1] + w_)
+        bank.slices = tuple(mod[:, o:o + w_] for o, w_ in zip(bank.offs, bank.widths))
+        ctx.bank = bank
+        ctx.save_for_backward(context, s, W)
+        return bank.slices
+
+    @_joined
+    def backward(ctx, *gs):
+        context, s, W = ctx.saved_tensors
+        bank = ctx.bank
+        if bank.dmod is None:
+            bank.dmod = torch.empty_like(bank.mod)
+        dmod = bank.dmod
+        for j, g in enumerate(gs):  # normally every g IS its slice of the slab (written in place by the norm's backward)
+            sl = dmod[:, bank.offs[j]:bank.offs[j] + bank.widths[j]]
+            if g is None:
+                sl.zero_()
+            elif g.data_ptr() != sl.data_ptr() or g.stride() != sl.stride():
+                sl.copy_(g)
+        dW, db = ops.linear_wgrad(dmod, s)
+        dctx = silu(context, ops.linear_dgrad(dmod, W)) if ctx.needs_input_grad[0] else None
+        out = [dctx, None]
+        for o, w_ in zip(bank.offs, bank.widths):
+            out += [dW[o:o + w_], db[o:o + w_]]
+        bank.dmod = None
+        return tuple(out)
+
+
+# ------------------------------------------------------------------------------------ sub-blocks
+class AdaCpeFn(torch.autograd.Function):
+    """x1 = x + PDNorm_LN(Linear(SubMConv3d_3(xs)))   (model.py:615-625, 661-663)."""
+
+    @_fwd
+    def forward(ctx, x, xs, mod, cw, cb, lw, lb, g, b, lvl, wt, bank, j):
+        same = xs is x
+        if wt is None:
+            wt = ops.conv_weight_t(cw)
+        c = ops.conv_fwd(xs, cw, cb, lvl.nbr27, lvl.order[0], w_t=wt, tap_plan=lvl.tap_plan)
+        l, _ = ops.linear_fwd(c, lw, lb)
+        y, mean, rstd = adaln_fwd(l, g, b, mod, lvl, res=x)
+        ctx.meta = (lvl, same, bank, j)
+        ctx.save_for_backward(xs, cw, lw, g, b, mod, c, l, mean, rstd, wt)
+        return y
+
+    @_joined
+    def backward(ctx, dy):
+        xs, cw, lw, g, b, mod, c, l, mean, rstd, wt = ctx.saved_tensors
+        lvl, same, bank, j = ctx.meta
+        dy = dy.contiguous()
+        dmod = bank.grad_slice(j)
+        dl, dg, db = adaln_bwd(dy, l, mean, rstd, g, b, mod, dmod, lvl)
+        dlw, dlb = ops.linear_wgrad(dl, c)
+        dc = ops.linear_dgrad(dl, lw)
+        dcw, dcb = ops.conv_wgrad(dc, xs, cw.shape, lvl.nbr27)
+        if same:
+            dx = ops.conv_dgrad(dc, cw, lvl.nbr27, lvl.order[0], add=dy, w_t=wt, lvl=lvl, tap_plan=lvl.tap_plan)
+            return dx, None, dmod, dcw, dcb, dlw, dlb, dg, db, None, None, None, None
+        dxs = ops.conv_dgrad(dc, cw, lvl.nbr27, lvl.order[0], w_t=wt, lvl=lvl, tap_plan=lvl.tap_plan)
+        return dy, dxs, dmod, dcw, dcb, dlw, dlb, dg, db, None, None, None, None
+
+
+class AdaSelfAttnFn(torch.autograd.Function):
+    """y = x + DropPath(drop(proj(PatchAttention(qkv(PDNorm_LN(x))))))   (model.py:664-668)."""
+
+    @_fwd
+    def forward(ctx, x, mod, g, b, wqkv, bqkv, qnw, qnb, knw, knb, wp, bp, lvl, H, drop_p, seed, attn_p, dpath, bank, j):
+        N, C = x.shape
+        d = C // H
+        n, mean, rstd = adaln_fwd(x, g, b, mod, lvl)
+        qkv, _ = ops.linear_fwd(n, wqkv, bqkv)
+        att = torch.empty(N, C, dtype=x.dtype, device=x.device)
+        lse = torch.empty(lvl.npad, H, dtype=torch.float32, device=x.device)
+        ops.attention_fwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles, lvl.n_self_tiles,
+                          (qnw, qnb), (knw, knb), att, lse, H, d, attn_p, mix_seed(seed, 1))
+        if dpath > 0.0:
+            br, _ = ops.linear_fwd(att, wp, bp, drop_p=drop_p, seed=seed)
+            y = ops.drop_path(br, x, dpath, mix_seed(seed, 5))
+        else:
+            y, _ = ops.linear_fwd(att, wp, bp, residual=x, drop_p=drop_p, seed=seed)
+        ctx.meta = (lvl, H, d, drop_p, seed, attn_p, float(dpath), bank, j)
+        ctx.save_for_backward(x, g, b, mod, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd)
+        return y
+
+    @_joined
+    def backward(ctx, dy):
+        x, g, b, mod, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd = ctx.saved_tensors
+        lvl, H, d, p, seed, attn_p, dpath, bank, j = ctx.meta
+        N, C = x.shape
+        dy = dy.contiguous()
+        dyb = ops.drop_path(dy, None, dpath, mix_seed(seed, 5)) if dpath > 0.0 else dy
+        dz = ops.dropout(dyb, p, seed)
+        dwp, dbp = ops.linear_wgrad(dz, att)
+        datt = ops.linear_dgrad(dz, wp)
+        dqkv = torch.empty(N, 3 * C, dtype=x.dtype, device=x.device)
+        extra = torch.empty(max(lvl.n_extra, 1), 2 * C, dtype=x.dtype, device=x.device)
+        gq, bq, gk, bk = ops.attention_bwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles,
+                                           lvl.self_blocks, lvl.n_self_tiles, (qnw, qnb), (knw, knb), att, datt, lse, dqkv, 3 * C, 0,
+                                           dqkv, 3 * C, C, 2 * C, 0, 0, H, d, attn_p, mix_seed(seed, 1), lvl.kext, lvl.ext_pos,
+                                           lvl.n_extra, extra)
+        dwqkv, dbqkv = ops.linear_wgrad(dqkv, n)
+        dn = ops.linear_dgrad(dqkv, wqkv)
+        dmod = bank.grad_slice(j)
+        dx, dg, db = adaln_bwd(dn, x, mean, rstd, g, b, mod, dmod, lvl, add=dy)
+        return (dx, dmod, dg, db, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp) + (None,) * 8
+
+
+class AdaFfnFn(torch.autograd.Function):
+    """y = x + DropPath(drop(fc2(drop(GELU(fc1(PDNorm_LN(x)))))))   (model.py:671-675, MLP :577-583)."""
+
+    @_fwd
+    def forward(ctx, x, mod, g, b, w1, b1, w2, b2, lvl, drop_p, seed, dpath, bank, j):
+        n, mean, rstd = adaln_fwd(x, g, b, mod, lvl)
+        a, hpre = ops.linear_fwd(n, w1, b1, act=ACT_GELU, save_pre=True, drop_p=drop_p, seed=seed)
+        if dpath > 0.0:
+            br, _ = ops.linear_fwd(a, w2, b2, drop_p=drop_p, seed=mix_seed(seed, 1))
+            y = ops.drop_path(br, x, dpath, mix_seed(seed, 5))
+        else:
+            y, _ = ops.linear_fwd(a, w2, b2, residual=x, drop_p=drop_p, seed=mix_seed(seed, 1))
+        ctx.meta = (lvl, drop_p, seed, float(dpath), bank, j)
+        ctx.save_for_backward(x, g, b, mod, w1, w2, n, hpre, a, mean, rstd)
+        return y
+
+    @_joined
+    def backward(ctx, dy):
+        x, g, b, mod, w1, w2, n, hpre, a, mean, rstd = ctx.saved_tensors
+        lvl, p, seed, dpath, bank, j = ctx.meta
+        dy = dy.contiguous()
+        dyb = ops.drop_path(dy, None, dpath, mix_seed(seed, 5)) if dpath > 0.0 else dy
+        dz2 = ops.dropout(dyb, p, mix_seed(seed, 1))
+        dw2, db2 = ops.linear_wgrad(dz2, a)
+        dh = ops.linear_dgrad(dz2, w2, pre=hpre, act=ACT_GELU, drop_p=p, seed=seed)
+        dw1, db1 = ops.linear_wgrad(dh, n)
+        dn = ops.linear_dgrad(dh, w1)
+        dmod = bank.grad_slice(j)
+        dx, dg, db = adaln_bwd(dn, x, mean, rstd, g, b, mod, dmod, lvl, add=dy)
+        return (dx, dmod, dg, db, dw1, db1, dw2, db2) + (None,) * 6
+
+
+class AdaStemFn(torch.autograd.Function):
+    """Embedding: GELU(PDNorm_BN(SubMConv3d_5(x)))   (model.py:844-861)."""
+
+    @_fwd
+    def forward(ctx, x, mod, cw, g, b, rmean, rvar, lvl, training, bank, j):
+        c = ops.conv_fwd(x, cw, None, lvl.nbr125, lvl.order[0])
+        y, mean, invstd = adabn_fwd(c, g, b, rmean, rvar, mod, lvl, training)
+        ctx.meta = (lvl, training, bank, j)
+        ctx.save_for_backward(x, mod, cw, g, b, c, mean, invstd)
+        return y
+
+    @_joined
+    def backward(ctx, dy):
+        x, mod, cw, g, b, c, mean, invstd = ctx.saved_tensors
+        lvl, training, bank, j = ctx.meta
+        dmod = bank.grad_slice(j)
+        dc, dg, db = adabn_bwd(dy.contiguous(), c, mean, invstd, g, b, mod, dmod, lvl, training)
+        dcw, _ = ops.conv_wgrad(dc, x, cw.shape, lvl.nbr125, need_bias=False, side=ctx.needs_input_grad[0])
+        dx = ops.conv_dgrad(dc, cw, lvl.nbr125, lvl.order[0], lvl=lvl) if ctx.needs_input_grad[0] else None
+        return dx, dmod, dcw, dg, db, None, None, None, None, None, None
+
+
+class AdaPoolFn(torch.autograd.Function):
+    """SerializedPooling: GELU(PDNorm_BN(segment_max(Linear(x))))   (model.py:760-790); the norm sees the pooled level's clouds."""
+
+    @_fwd
+    def forward(ctx, x, mod, w, bias, g, b, rmean, rvar, child, training, bank, j):
+        proj, _ = ops.linear_fwd(x, w, bias)
+        C = w.shape[0]
+        pooled = torch.empty(child.n, C, dtype=x.dtype, device=x.device)
+        arg = torch.empty(child.n, C, dtype=torch.int32, device=x.device)
+        call("lotus_pool_max_fwd", proj, child.members, child.seg_start, child.n, C, pooled, arg)
+        y, mean, invstd = adabn_fwd(pooled, g, b, rmean, rvar, mod, child, training)
+        ctx.meta = (child, training, bank, j)
+        ctx.save_for_backward(x, mod, w, g, b, pooled, arg, mean, invstd)
+        return y
+
+    @_joined
+    def backward(ctx, dy):
+        x, mod, w, g, b, pooled, arg, mean, invstd = ctx.saved_tensors
+        child, training, bank, j = ctx.meta
+        C = w.shape[0]
+        dmod = bank.grad_slice(j)
+        dpool, dg, db = adabn_bwd(dy.contiguous(), pooled, mean, invstd, g, b, mod, dmod, child, training)
+        dproj = torch.empty(x.shape[0], C, dtype=x.dtype, device=x.device)
+        call("lotus_pool_max_bwd", dpool, arg, child.cluster, x.shape[0], C, dproj)
+        dw, dbias = ops.linear_wgrad(dproj, x)
+        dx = ops.linear_dgrad(dproj, w)
+        return dx, dmod, dw, dbias, dg, db, None, None, None, None, None, None
+
+
+class AdaUnpoolFn(torch.autograd.Function):
+    """SerializedUnpooling: skip = GELU(PDNorm_BN(Linear_skip(parent))), up = GELU(PDNorm_BN(Linear(point)));
+    returns (skip + up[cluster], skip)   (model.py:817-828).  `up` is modulated per cloud of the coarse level, `skip` per
+    cloud of the fine one."""
+
+    @_fwd
+    def forward(ctx, xc, xp, modu, mods, wu, bu, gu, betau, rmu, rvu, ws_, bs, gs, betas, rms, rvs, child, lvl, training, bank,
+                ju, js):
+        lu, _ = ops.linear_fwd(xc, wu, bu)
+        ls, _ = ops.linear_fwd(xp, ws_, bs)
+        up, mu, iu = adabn_fwd(lu, gu, betau, rmu, rvu, modu, child, training)
+        skip, ms, is_ = adabn_fwd(ls, gs, betas, rms, rvs, mods, lvl, training)
+        x = torch.empty_like(skip)
+        call("lotus_unpool_fwd", skip, up, child.cluster, skip.shape[0], skip.shape[1], x)
+        ctx.meta = (child, lvl, training, bank, ju, js)
+        ctx.save_for_backward(xc, xp, modu, mods, wu, gu, betau, ws_, gs, betas, lu, ls, mu, iu, ms, is_)
+        return x, skip
+
+    @_joined
+    def backward(ctx, dx, dskip):
+        xc, xp, modu, mods, wu, gu, betau, ws_, gs, betas, lu, ls, mu, iu, ms, is_ = ctx.saved_tensors
+        child, lvl, training, bank, ju, js = ctx.meta
+        C = wu.shape[0]
+        dx = dx.contiguous()
+        dup = torch.empty(child.n, C, dtype=dx.dtype, device=dx.device)
+        call("lotus_unpool_bwd", dx, child.members, child.seg_start, child.n, C, dup)
+        dsk = ops.add(dx, dskip.contiguous()) if dskip is not None else dx
+        dmu, dms = bank.grad_slice(ju), bank.grad_slice(js)
+        dlu, dgu, dbetau = adabn_bwd(dup, lu, mu, iu, gu, betau, modu, dmu, child, training)
+        dls, dgs, dbetas = adabn_bwd(dsk, ls, ms, is_, gs, betas, mods, dms, lvl, training)
+        dwu, dbu = ops.linear_wgrad(dlu, xc)
+        dxc = ops.linear_dgrad(dlu, wu)
+        dws, dbs = ops.linear_wgrad(dls, xp)
+        dxp = ops.linear_dgrad(dls, ws_)
+        return (dxc, dxp, dmu, dms, dwu, dbu, dgu, dbetau, None, None, dws, dbs, dgs, dbetas) + (None,) * 8
+
+
+# ------------------------------------------------------------------------------------ modules
+class PDNorm(nn.Module):
+    """Parameter container with the layout of model.py:257-278 (decouple = False, adaptive = True):
+    `norm` (nn.LayerNorm / nn.BatchNorm1d) and `modulation` = Sequential(SiLU, Linear(context, 2C))."""
+
+    def __init__(self, norm, c, context_channels=256):
+        super().__init__()
+        self.norm = norm
+        self.modulation = nn.Sequential(nn.SiLU(), nn.Linear(context_channels, 2 * c))
+
+    @property
+    def num_batches_tracked(self):
+        return self.norm.num_batches_tracked
+
+
+def _pd_ln(c, ctx):
+    return PDNorm(nn.LayerNorm(c), c, ctx)
+
+
+def _pd_bn(c, ctx):
+    return PDNorm(_bn(c), c, ctx)
+
+
+class AdaBlock(nn.Module):
+    """model.py:586-680 with PDNorm LayerNorms (cpe.2, norm1, norm2); attn.q_norm / k_norm stay plain."""
+
+    def __init__(self, c, h, mlp_ratio, ctx):
+        super().__init__()
+        self.num_heads = h
+        self.cpe = nn.Sequential(SubMConv3d(c, c, 3, bias=True), nn.Linear(c, c), _pd_ln(c, ctx))
+        self.norm1 = nn.Sequential(_pd_ln(c, ctx))
+        self.attn = _Attn(c, h)
+        self.norm2 = nn.Sequential(_pd_ln(c, ctx))
+        self.mlp = nn.Sequential(_MLP(c, int(c * mlp_ratio)))
+
+
+class _AdaDown(nn.Module):
+    def __init__(self, cin, cout, ctx):
+        super().__init__()
+        self.proj = nn.Linear(cin, cout)
+        self.norm = nn.Sequential(_pd_bn(cout, ctx))
+
+
+class _AdaUp(nn.Module):
+    def __init__(self, cin, cskip, cout, ctx):
+        super().__init__()
+        self.proj = nn.Sequential(nn.Linear(cin, cout), _pd_bn(cout, ctx))
+        self.proj_skip = nn.Sequential(nn.Linear(cskip, cout), _pd_bn(cout, ctx))
+
+
+class _AdaStem(nn.Module):
+    def __init__(self, cin, cout, ctx):
+        super().__init__()
+        self.conv = SubMConv3d(cin, cout, 5, bias=False)
+        self.norm = _pd_bn(cout, ctx)
+
+
+class _AdaEmbedding(nn.Module):
+    def __init__(self, cin, cout, ctx):
+        super().__init__()
+        self.stem = _AdaStem(cin, cout, ctx)
+
+
+def check_pdnorm_options(pdnorm_bn, pdnorm_ln, pdnorm_decouple, pdnorm_adaptive, pdnorm_affine, pdnorm_only_decoder):
+    """The one PDNorm combination built here: the reference YAML's (simple_policy_ptv3.yaml:93 ff.)."""
+    want = dict(pdnorm_bn=True, pdnorm_ln=True, pdnorm_decouple=False, pdnorm_adaptive=True, pdnorm_affine=True,
+                pdnorm_only_decoder=False)
+    got = dict(pdnorm_bn=pdnorm_bn, pdnorm_ln=pdnorm_ln, pdnorm_decouple=pdnorm_decouple, pdnorm_adaptive=pdnorm_adaptive,
+               pdnorm_affine=pdnorm_affine, pdnorm_only_decoder=pdnorm_only_decoder)
+    bad = [f"{k}={got[k]}" for k in want if bool(got[k]) != want[k]]
+    if bad:
+        raise NotImplementedError(f"SimplePolicyPTV3AdaNorm builds pdnorm_bn = pdnorm_ln = pdnorm_adaptive = pdnorm_affine = True, "
+                                  f"pdnorm_decouple = pdnorm_only_decoder = False only; unsupported: {bad}")
+
+
+class PointTransformerV3AdaNorm(PointTransformerV3CA):
+    """PointTransformerV3(pdnorm_bn = pdnorm_ln = pdnorm_adaptive = True), model.py:864-1100: every stage a chain of Blocks.
+    forward(data_dict) takes data_dict["context"] = [B, pdnorm_context_channels], one vector per cloud.  The front end, its
+    prefetch, seeds and pack helpers are PointTransformerV3CA's."""
+
+    def __init__(self, in_channels=6, order=("z", "z-trans", "hilbert", "hilbert-trans"), stride=(2, 2, 2, 2),
+                 enc_depths=(2, 2, 2, 6, 2), enc_channels=(32, 64, 128, 256, 512), enc_num_head=(2, 4, 8, 16, 32),
+                 enc_patch_size=(1024,) * 5, dec_depths=(2, 2, 2, 2), dec_channels=(64, 64, 128, 256),
+                 dec_num_head=(4, 4, 8, 16), dec_patch_size=(1024,) * 4, mlp_ratio=4, ctx_channels=256,
+                 qkv_bias=True, qk_scale=None, qk_norm=False, attn_drop=0.0, proj_drop=0.0, drop_path=0.3,
+                 pre_norm=True, shuffle_orders=True, enable_rpe=False, enable_flash=True, upcast_attention=False,
+                 upcast_softmax=False, cls_mode=False, pdnorm_bn=True, pdnorm_ln=True, pdnorm_decouple=False,
+                 pdnorm_adaptive=True, pdnorm_context_channels=256, pdnorm_affine=True,
+                 pdnorm_conditions=("ScanNet", "S3DIS", "Structured3D"), pdnorm_only_decoder=False,
+                 add_coords_in_attn=False, scaled_cosine_attn=False):
+        nn.Module.__init__(self)
+        check_pdnorm_options(pdnorm_bn, pdnorm_ln, pdnorm_decouple, pdnorm_adaptive, pdnorm_affine, pdnorm_only_decoder)
+        unsupported = dict(enable_rpe=enable_rpe, cls_mode=cls_mode, scaled_cosine_attn=scaled_cosine_attn,
+                           not_flash=not enable_flash, not_qk_norm=not qk_norm, not_pre_norm=not pre_norm,
+                           no_qkv_bias=not qkv_bias, qk_scale=qk_scale is not None,
+                           add_coords=add_coords_in_attn not in (False, "none", None),
+                           depth_lt_1=any(d < 1 for d in list(enc_depths) + list(dec_depths)),
+                           stride_ne_2=any(s != 2 for s in stride),
+                           patch_ne_128=any(p > 128 for p in list(enc_patch_size) + list(dec_patch_size)))
+        bad = [k for k, v in unsupported.items() if v]
+        if bad:
+            raise NotImplementedError(f"lotus-hip builds the published 3D-LOTUS configuration family only; unsupported: {bad}")
+        if len(set(enc_patch_size) | set(dec_patch_size)) != 1:
+            raise NotImplementedError("all patch sizes must be equal")
+        ctx = int(pdnorm_context_channels)
+        self.context_channels = ctx
+        self.num_stages = len(enc_depths)
+        self.order = list(order)
+        self.shuffle_orders = shuffle_orders
+        self.proj_drop, self.attn_drop = float(proj_drop), float(attn_drop)
+        self.enc_channels, self.dec_channels = list(enc_channels), list(dec_channels) + [enc_channels[-1]]
+        self.enc_depths, self.dec_depths = [int(d) for d in enc_depths], [int(d) for d in dec_depths]
+        self.frontend = FrontEnd(self.num_stages, patch_size=enc_patch_size[0], orders=self.order,
+                                 n_patch_orders=max(self.enc_depths + self.dec_depths),
+                                 conv_widths=[max(e, d) for e, d in zip(self.enc_channels, self.dec_channels)])
+        ed = torch.linspace(0, drop_path, sum(self.enc_depths)).tolist()
+        dd = torch.linspace(0, drop_path, sum(self.dec_depths)).tolist() if self.dec_depths else []
+        self.enc_drop_path = [ed[sum(self.enc_depths[:s]):sum(self.enc_depths[:s + 1])] for s in range(self.num_stages)]
+        self.dec_drop_path = [list(reversed(dd[sum(self.dec_depths[:s]):sum(self.dec_depths[:s + 1])]))
+                              for s in range(self.num_stages - 1)]
+
+        self.embedding = _AdaEmbedding(in_channels, enc_channels[0], ctx)
+        self.enc = nn.Sequential()
+        for s in range(self.num_stages):
+            enc = nn.Sequential()
+            if s > 0:
+                enc.add_module("down", _AdaDown(enc_channels[s - 1], enc_channels[s], ctx))
+            for i in range(self.enc_depths[s]):
+                enc.add_module(f"block{i}", AdaBlock(enc_channels[s], enc_num_head[s], mlp_ratio, ctx))
+            self.enc.add_module(f"enc{s}", enc)
+        self.dec = nn.Sequential()
+        dc = self.dec_channels
+        for s in reversed(range(self.num_stages - 1)):
+            dec = nn.Sequential()
+            dec.add_module("up", _AdaUp(dc[s + 1], enc_channels[s], dc[s], ctx))
+            for i in range(self.dec_depths[s]):
+                dec.add_module(f"block{i}", AdaBlock(dc[s], dec_num_head[s], mlp_ratio, ctx))
+            self.dec.add_module(f"dec{s}", dec)
+        self._blocks = [m for m in self.modules() if isinstance(m, AdaBlock)]
+        self._block_level = {}
+        for s in range(self.num_stages):
+            for m in self.enc[s].children():
+                if isinstance(m, AdaBlock):
+                    self._block_level[id(m)] = s
+        for i, s in enumerate(reversed(range(self.num_stages - 1))):
+            for m in self.dec[i].children():
+                if isinstance(m, AdaBlock):
+                    self._block_level[id(m)] = s
+        self._pdnorms = [m for m in self.modules() if isinstance(m, PDNorm)]  # slice j of the modulation bank = norm j
+        self._pd_index = {id(m): j for j, m in enumerate(self._pdnorms)}
+        self._cablocks, self._cab_index, self._pair_params = [], {}, {}
+        self.kv_group = False
+        self._step = None
+        self._seed_base = None
+        self.order_perms = None
+        self._pending, self._deferred, self._fe_stream = None, None, None
+        self._nbt = None
+        self._sync_bn_checked = False
+        self.register_load_state_dict_post_hook(lambda m, _keys: setattr(m, "_step", None))
+
+    def _check_sync_bn(self):
+        """SyncBatchNorm under modulation (its backward across ranks) is not built: refuse data-parallel runs instead of
+        normalising per rank."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("SimplePolicyPTV3AdaNorm runs on one process: a process group with world size "
+                                      f"{dist.get_world_size()} > 1 (SyncBatchNorm under PDNorm modulation) is not supported")
+        self._sync_bn_checked = True
+
+    def _mod_params(self):
+        wb = []
+        for m in self._pdnorms:
+            lin = m.modulation[1]
+            wb += [lin.weight, lin.bias]
+        return wb
+
+    def forward(self, data_dict, return_dec_layers=False):
+        feat, src, counts, ctx_counts, context = self._front_inputs(data_dict)
+        if context is None or context.dim() != 2 or context.shape[0] != len(counts) or context.shape[1] != self.context_channels:
+            raise ValueError(f"PointTransformerV3AdaNorm needs one context vector per cloud: [{len(counts)}, "
+                             f"{self.context_channels}], got {None if context is None else tuple(context.shape)}")
+        if context.dtype != torch.float32 or feat.dtype != torch.float32:
+            raise NotImplementedError("SimplePolicyPTV3AdaNorm stores activations in fp32 only")
+        pend, self._pending = self._pending, None
+        if pend is not None and pend["pc_fts"] is src and pend["counts"] == list(counts):
+            levels = self.frontend.finish(pend, ctx_counts, need_coord=True)
+        else:
+            perms = self.order_perms if self.order_perms is not None else draw_order_perms(self.num_stages, self.shuffle_orders)
+            levels = self.frontend.build(src, counts, ctx_counts, perms, need_coord=True)
+        nxt, self._deferred = self._deferred, None
+        if nxt is not None:
+            nxt()
+        self.last_n_dup = levels[0].n_dup
+        training = self.training
+        if not self._sync_bn_checked:
+            self._check_sync_bn()
+        p = self.proj_drop if training else 0.0
+        pa = self.attn_drop if training else 0.0
+        base = self._seeds() if training else 0
+        self.last_seed = base
+        if training:
+            nbt = self._bn_counters()
+            if nbt:
+                torch._foreach_add_(nbt, 1)
+        site = 0
+        pid = self._pd_index
+        need = [b for b in self._blocks if not ops.conv_tap_active(levels[self._block_level[id(b)]], b.cpe[0].weight.shape[0])]
+        packs = dict(zip(need, ops.prepack_conv_weights([b.cpe[0].weight for b in need])))
+        for b in self._blocks:
+            packs.setdefault(b, ops.no_pack(feat.device))
+        n_ord = len(self.order)
+
+        bank = ModBank()
+        mods = ModAllFn.apply(context, bank, *self._mod_params())
+        st = self.embedding.stem
+        nb = st.norm.norm
+        x = AdaStemFn.apply(feat, mods[pid[id(st.norm)]], st.conv.weight, nb.weight, nb.bias, nb.running_mean, nb.running_var,
+                            levels[0], training, bank, pid[id(st.norm)])
+        ops.sync_side_stream()  # the packed convolution weights
+
+        def run_block(blk, x, xs, lvl, si, dpath):
+            c0, c1, pc = blk.cpe[0], blk.cpe[1], blk.cpe[2]
+            x = AdaCpeFn.apply(x, xs, mods[pid[id(pc)]], c0.weight, c0.bias, c1.weight, c1.bias, pc.norm.weight, pc.norm.bias,
+                               lvl, packs[blk], bank, pid[id(pc)])
+            a, n1 = blk.attn, blk.norm1[0]
+            x = AdaSelfAttnFn.apply(x, mods[pid[id(n1)]], n1.norm.weight, n1.norm.bias, a.qkv.weight, a.qkv.bias, a.q_norm.weight,
+                                    a.q_norm.bias, a.k_norm.weight, a.k_norm.bias, a.proj.weight, a.proj.bias, lvl, blk.num_heads,
+                                    p, si, pa, dpath, bank, pid[id(n1)])
+            m, n2 = blk.mlp[0], blk.norm2[0]
+            return AdaFfnFn.apply(x, mods[pid[id(n2)]], n2.norm.weight, n2.norm.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight,
+                                  m.fc2.bias, lvl, p, mix_seed(si, 2), dpath, bank, pid[id(n2)])
+
+        skips = []
+        for s in range(self.num_stages):
+            enc, lvl = self.enc[s], levels[s]
+            site += 1
+            seed = mix_seed(base, site)
+            if s > 0:
+                d = enc.down
+                pn = d.norm[0]
+                x = AdaPoolFn.apply(x, mods[pid[id(pn)]], d.proj.weight, d.proj.bias, pn.norm.weight, pn.norm.bias,
+                                    pn.norm.running_mean, pn.norm.running_var, lvl, training, bank, pid[id(pn)])
+            for i in range(self.enc_depths[s]):
+                si = seed if i == 0 else mix_seed(seed, 16 + i)
+                dpath = self.enc_drop_path[s][i] if training else 0.0
+                x = run_block(getattr(enc, f"block{i}"), x, x, lvl.for_order(i % n_ord), si, dpath)
+            skips.append(x)
+        outs = [self._pack(x, levels[-1])]
+        for i, s in enumerate(reversed(range(self.num_stages - 1))):
+            dec, lvl, child = self.dec[i], levels[s], levels[s + 1]
+            site += 1
+            seed = mix_seed(base, site)
+            u, us = dec.up.proj, dec.up.proj_skip
+            nu, ns = u[1], us[1]
+            x, skip = AdaUnpoolFn.apply(x, skips[s], mods[pid[id(nu)]], mods[pid[id(ns)]], u[0].weight, u[0].bias, nu.norm.weight,
+                                        nu.norm.bias, nu.norm.running_mean, nu.norm.running_var, us[0].weight, us[0].bias,
+                                        ns.norm.weight, ns.norm.bias, ns.norm.running_mean, ns.norm.running_var, child, lvl,
+                                        training, bank, pid[id(nu)], pid[id(ns)])
+            for j in range(self.dec_depths[s]):
+                si = seed if j == 0 else mix_seed(seed, 16 + j)
+                dpath = self.dec_drop_path[s][j] if training else 0.0
+                # the first Block of a decoder stage convolves the proj_skip branch (its sparse_conv_feat), SURVEY.md Trap 3
+                x = run_block(getattr(dec, f"block{j}"), x, skip if j == 0 else x, lvl.for_order(j % n_ord), si, dpath)
+            outs.append(self._pack(x, lvl))
+        return outs if return_dec_layers else outs[-1]
+
+
+def cloud_context(txt_ctx, txt_w, lens):
+    """txt_reduce == 'attn' (simple_policy_ptv3.py:204-211): per cloud, softmax over its tokens of txt_attn_fc, weighting the
+    projected tokens.  txt_ctx [T, C], txt_w [T, 1], lens: tokens per cloud -> [B, C].  Padded to the longest instruction:
+    every index but the padding one is gathered once, so the backward pass has no colliding accumulation."""
+    B, L = len(lens), max(lens)
+    T = txt_ctx.shape[0]
+    idx = np.full((B, L), T, dtype=np.int64)
+    st = 0
+    for b, n in enumerate(lens):
+        idx[b, :n] = np.arange(st, st + n)
+        st += n
+    idx_t = torch.from_numpy(idx).to(txt_ctx.device)
+    w = torch.cat([txt_w[:, 0], txt_w.new_full((1,), float("-inf"))])[idx_t]          # [B, L]
+    p = torch.softmax(w, 1)
+    tok = torch.cat([txt_ctx, txt_ctx.new_zeros(1, txt_ctx.shape[1])])[idx_t]          # [B, L, C]
+    return (p.unsqueeze(-1) * tok).sum(1)

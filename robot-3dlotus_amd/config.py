@@ -158,14 +158,26 @@ MP_TINYCTX_OVERRIDES = MP_TINY_OVERRIDES + ["action_config.use_ee_pose", "True"]
 PERACT_OVERRIDES = V1_OVERRIDES + ["action_config.txt_reduce", "attn"]
 
 
+# SimplePolicyPTV3AdaNorm (simple_policy_ptv3.py:160-373): the same networks with the YAML's adaptive PDNorm switches
+# (simple_policy_ptv3.yaml:93 ff.) instead of cross attention
+ADANORM_SWITCHES = ["model_class", "SimplePolicyPTV3AdaNorm", "ptv3_config.pdnorm_bn", "True", "ptv3_config.pdnorm_ln", "True",
+                    "ptv3_config.pdnorm_adaptive", "True", "ptv3_config.pdnorm_decouple", "False",
+                    "ptv3_config.pdnorm_affine", "True", "ptv3_config.pdnorm_only_decoder", "False"]
+ADANORM_OVERRIDES = {"adanorm_v1": V1_OVERRIDES + ADANORM_SWITCHES, "adanorm_tiny": TINY_OVERRIDES + ADANORM_SWITCHES,
+                     "adanorm_tinyctx": TINYCTX_OVERRIDES + ADANORM_SWITCHES}
+
+
 def preset(name="v1"):
     """'v1' / 'tiny': 3D-LOTUS policy; 'peract': the RLBench-18task (PerAct) variant of BASELINE configs[4] (same network;
-    its bf16 compute mode is ops.set_gemm_precision("bf16")); 'mp' / 'mp_tiny': 3D-LOTUS++ motion planner (configs[3])."""
+    its bf16 compute mode is ops.set_gemm_precision("bf16")); 'mp' / 'mp_tiny': 3D-LOTUS++ motion planner (configs[3]);
+    'adanorm_v1' / 'adanorm_tiny' / 'adanorm_tinyctx': the policy networks as SimplePolicyPTV3AdaNorm (adaptive PDNorm)."""
     if name in ("mp", "mp_tiny", "mp_tinyctx"):
         model = copy.deepcopy(_YAML_MODEL)
         model["model_class"] = _YAML_MP_DELTA["model_class"]
         model["action_config"].update(_YAML_MP_DELTA["action_config"])
         return to_cfg(merge_overrides(model, {"mp": MP_OVERRIDES, "mp_tiny": MP_TINY_OVERRIDES, "mp_tinyctx": MP_TINYCTX_OVERRIDES}[name]))
+    if name in ADANORM_OVERRIDES:
+        return load_model_config(None, ADANORM_OVERRIDES[name])
     return load_model_config(None, {"v1": V1_OVERRIDES, "tiny": TINY_OVERRIDES, "peract": PERACT_OVERRIDES,
                                     "tinydeep": TINYDEEP_OVERRIDES, "tinyctx": TINYCTX_OVERRIDES}[name])
 

@@ -287,10 +287,72 @@ class SimplePolicyPTV3CA(BaseModel):
 
 
 
+class SimplePolicyPTV3AdaNorm(SimplePolicyPTV3CA):
+    """simple_policy_ptv3.py:160-373: the instruction (+ pose, + step) enters the point backbone through adaptive PDNorm
+    (adanorm.PointTransformerV3AdaNorm) — one context vector per cloud — instead of cross attention.  Head, losses, decode,
+    forward contract and `last_pred` are SimplePolicyPTV3CA's; the state_dict has the reference's layout (PDNorm sites
+    `<site>.norm.*` + `<site>.modulation.1.*`, `txt_attn_fc` only for txt_reduce == 'attn', no CABlocks).
+    fp32 activation storage, one process."""
+
+    def __init__(self, config):
+        from .adanorm import PointTransformerV3AdaNorm
+
+        BaseModel.__init__(self)
+        config = to_cfg(config)
+        self.config = config
+        p3 = {k: v for k, v in config.ptv3_config.items() if k in _PTV3_KEYS}
+        p3.setdefault("pdnorm_only_decoder", False)  # (simple_policy_ptv3.py:165-167)
+        act = config.action_config
+        p3["pdnorm_context_channels"] = act.context_channels
+        self.ptv3_model = PointTransformerV3AdaNorm(**p3)
+        if act.txt_reduce not in ("mean", "attn"):
+            raise NotImplementedError(f"txt_reduce={act.txt_reduce!r}: SimplePolicyPTV3AdaNorm builds 'mean' and 'attn'")
+        self.txt_fc = nn.Linear(act.txt_ft_size, act.context_channels)
+        if act.txt_reduce == "attn":
+            self.txt_attn_fc = nn.Linear(act.txt_ft_size, 1)
+        if act.use_ee_pose:
+            self.pose_embedding = RobotPoseEmbedding(act.context_channels)
+        if act.use_step_id:
+            self.stepid_embedding = nn.Embedding(act.max_steps, act.context_channels)
+        self.act_proj_head = ActionHead(act.reduce, act.pos_pred_type, act.rot_pred_type,
+                                        config.ptv3_config.dec_channels[0], act.dim_actions, dropout=act.dropout,
+                                        voxel_size=act.voxel_size, pos_bins=act.pos_bins)
+        self.apply(self._init_weights)
+
+    def prepare_ptv3_batch(self, batch):
+        """simple_policy_ptv3.py:193-223: context = txt_fc(txt_embeds), reduced to one vector per cloud ('attn': softmax of
+        txt_attn_fc over the cloud's tokens; 'mean': the instruction must be ONE token per cloud, instr_embed_type='last'),
+        plus pose_embedding(ee_poses) / stepid_embedding(step_ids) when enabled."""
+        from .adanorm import cloud_context
+
+        txt = batch["txt_embeds"].contiguous()
+        lens = [int(v) for v in batch["txt_lens"]]
+        act = self.config.action_config
+        if act.txt_reduce == "mean" and any(n != 1 for n in lens):
+            raise ValueError(f"txt_reduce='mean' takes one instruction token per cloud (instr_embed_type='last'); txt_lens={lens}")
+        ctx = ops.LinearFn.apply(txt, self.txt_fc.weight, self.txt_fc.bias)
+        if act.txt_reduce == "attn":
+            w = ops.LinearFn.apply(txt, self.txt_attn_fc.weight, self.txt_attn_fc.bias)
+            ctx = cloud_context(ctx, w, lens)
+        if act.use_ee_pose:
+            ctx = ctx + self.pose_embedding(batch["ee_poses"].float())
+        if act.use_step_id:
+            ctx = ctx + self.stepid_embedding(batch["step_ids"].long())
+        B = len(batch["npoints_in_batch"])
+        return {"coord": batch["pc_fts"][:, :3], "grid_size": act.voxel_size, "offset": batch["offset"],
+                "feat": batch["pc_fts"], "context": ctx.contiguous(), "counts": list(batch["npoints_in_batch"]),
+                "context_counts": [1] * B}
+
+    def forward(self, batch, compute_loss=False, **kwargs):
+        if self.act_storage == "bf16":
+            raise NotImplementedError("SimplePolicyPTV3AdaNorm: act_storage='bf16' is not built (fp32 activations only)")
+        return super().forward(batch, compute_loss, **kwargs)
+
 
 def _factory():
     from .motion_planner import MotionPlannerPTV3CA
-    return {"SimplePolicyPTV3CA": SimplePolicyPTV3CA, "MotionPlannerPTV3CA": MotionPlannerPTV3CA}
+    return {"SimplePolicyPTV3CA": SimplePolicyPTV3CA, "MotionPlannerPTV3CA": MotionPlannerPTV3CA,
+            "SimplePolicyPTV3AdaNorm": SimplePolicyPTV3AdaNorm}
 
 
 class _Factory(dict):
@@ -302,4 +364,4 @@ class _Factory(dict):
         return dict.__getitem__(self, k)
 
 
-MODEL_FACTORY = _Factory({"SimplePolicyPTV3CA": SimplePolicyPTV3CA})
+MODEL_FACTORY = _Factory({"SimplePolicyPTV3CA": SimplePolicyPTV3CA, "SimplePolicyPTV3AdaNorm": SimplePolicyPTV3AdaNorm})
