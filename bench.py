@@ -1,6 +1,6 @@
 """bench.py — keystep-samples/sec (train fwd+bwd) of the 3D-LOTUS v1 policy on N MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 
 N > 1: one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process is
 one rank; started bare, `--gpus N` re-executes itself through `python -m torch.distributed.run --nproc-per-node N`
@@ -11,9 +11,14 @@ One "step" = forward + loss + backward (+ gradient all-reduce when N > 1) of the
 synthetic GemBench-shape batch of 16 key-step clouds x 4096 points per GPU (BASELINE.json
 configs[1]; weak scaling: 16 clouds per rank).  Inputs are resident in HBM before the timed
 region.  Dropout is active (train mode, reference rates), weights are random-init of the v1
-architecture.  Prints ONE JSON line on rank 0 with the metric, the roofline object of the
-dominant kernel family (dense fp32-MFMA linear layers, timed live with HIP events by replaying
-the step's launch list) and the CPU baseline (the oracle timed on the host cores).
+architecture.  Prints ONE JSON line on rank 0 with the metric.
+
+A plain run does only what that headline needs: set-up, warm-up, the timed steps, --dump-outputs and the line.  --full
+adds, after the timed steps, everything else the benchmark measures or checks: the roofline object of the dominant kernel
+family (dense fp32-MFMA linear layers, timed live with HIP events by replaying the step's launch list) with the committed
+counter passes of this library build, the opt-in operand precisions, the step with the optimizer, new host batches, the
+data-parallel communication figures, the other BASELINE workloads and the CPU baseline (the oracle timed on the host
+cores).  The --no-* switches leave single parts of --full out.
 """
 import argparse
 import json
@@ -41,7 +46,7 @@ def side_workload(extra, timeout_s=300):
     return the essentials of its JSON line: side measurements printed next to the headline, never as `value`."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "20", "--warmup", "6", "--no-cpu-baseline", "--no-fresh-batches",
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "20", "--warmup", "6", "--full", "--no-cpu-baseline", "--no-fresh-batches",
            "--no-other-modes", "--no-side-workloads"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     try:
@@ -258,8 +263,12 @@ def main():
     ap.add_argument("--ragged", action="store_true",
                     help="clouds of n ~ U(npoints / 2, npoints) points (SURVEY 8d: the ragged variant of the canonical batch; the "
                          "headline is quoted on exactly npoints per cloud)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the benchmark measures or checks (roofline and counter "
+                         "figures, opt-in precisions, optimizer step, new host batches, communication figures, other workloads, CPU "
+                         "baseline); a plain run does only what the headline needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline and counter figures")
     ap.add_argument("--with-optimizer", action="store_true",
                     help="also run lr schedule + clip_grad_norm_(10) + fused AdamW inside every step (SURVEY 8f rank 1); "
                          "the headline metric of BASELINE.json is forward + backward only, so this is off by default")
@@ -271,14 +280,15 @@ def main():
                          "clouds augmented as the PerAct job script does (aug_max_rot 45 -> duplicate voxels), bf16 operands — "
                          "side measurements, same step structure")
     ap.add_argument("--no-fresh-batches", action="store_true",
-                    help="skip the end-to-end side measurement (a new pinned host batch per step: H2D + front-end in the timed region)")
+                    help="--full: skip the end-to-end side measurement (a new pinned host batch per step: H2D + front-end in the timed region)")
     ap.add_argument("--gemm-precision", choices=["fp32", "bf16x3", "bf16"], default="fp32",
                     help="operand precision of the dense fwd/dgrad products: fp32 = exact fp32 MFMA (default, the parity mode "
                          "the headline is quoted in); bf16x3 / bf16 are the opt-in faster modes (DESIGN.md 4)")
-    ap.add_argument("--no-other-modes", action="store_true", help="skip the bf16x3 / bf16 side measurement")
+    ap.add_argument("--no-other-modes", action="store_true",
+                    help="--full: skip the bf16x3 / bf16 side measurement (and with it the optimizer step and the other workloads)")
     ap.add_argument("--no-side-workloads", action="store_true",
-                    help="skip the side measurements of the other BASELINE workloads (PerAct bf16 at 16 / 64 clouds, motion planner)")
-    ap.add_argument("--gemm-report", default=None, help="write per-shape GEMM timings (diagnostic) to this file")
+                    help="--full: skip the side measurements of the other BASELINE workloads (PerAct bf16 at 16 / 64 clouds, motion planner)")
+    ap.add_argument("--gemm-report", default=None, help="--full: write per-shape GEMM timings (diagnostic) to this file")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (losses, parameter gradients, head predictions) to "
                          "DIR/<name>.npy; the inputs are the same in every run with the same arguments")
@@ -286,6 +296,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.gemm_report and not (args.full and not args.no_roofline):
+        ap.error("--gemm-report extends the roofline figure: it needs --full (without --no-roofline)")
+    if not args.full:  # a plain run: nothing after the timed steps but --dump-outputs and the JSON line
+        args.no_cpu_baseline = args.no_roofline = args.no_other_modes = args.no_fresh_batches = args.no_side_workloads = True
     if args.cpu_baseline_only:
         import robot_3dlotus_amd  # noqa: F401
         print(json.dumps(cpu_baseline_measure()), flush=True)
@@ -441,10 +455,10 @@ def main():
     if args.dump_outputs and rank == 0:  # before any further step() overwrites the gradients
         dump_outputs(args.dump_outputs, losses, model, params)
     bn_msgs = parallel.BN_MESSAGES - bn_msgs0
-    # per-rank communication figures (outside the timed region): GPU time the backward stream waited in finish() per step,
-    # GPU time of the SyncBN statistics messages of one extra step, and the point counts the ranks hold
+    # per-rank communication figures (outside the timed region, --full): GPU time the backward stream waited in finish() per
+    # step, GPU time of the SyncBN statistics messages of one extra step, and the point counts the ranks hold
     comm_stats = None
-    if reducer is not None:
+    if reducer is not None and args.full:
         exposed = reducer.exposed_comm_ms()
         parallel.BN_TIMING = []
         step()
@@ -625,7 +639,8 @@ def main():
             out["config"]["workload"] += f"; RAGGED clouds n ~ U({args.npoints // 2}, {args.npoints}) ({sum(host_batch['npoints_in_batch'])} points on rank 0)"
         if reducer is not None:
             sizes = [(hi_ - lo_) * 4 / 2 ** 20 for lo_, hi_ in reducer.buckets]
-            out["comm"] = comm_stats
+            if comm_stats is not None:
+                out["comm"] = comm_stats
             out["reducer"] = {"buckets": len(sizes), "bucket_mb": [round(x, 1) for x in sizes], "last_bucket_mb": round(sizes[-1], 1),
                               "gradient_mb": round(sum(sizes), 1), "syncbn_messages_per_step": f"{bn_msgs / max(1, args.steps):.0f} (counted; one fp64 message per BN layer or merged pair and direction, own communicator)",
                               "points_rank0": int(sum(host_batch["npoints_in_batch"])),

@@ -11,7 +11,7 @@ BENCH_ARGS="--workload peract" bash profiles/pmc_passes.sh ${TAG}p > gpurun_out/
 rm -f gpurun_out/prof/${TAG}z_*
 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o ${TAG}z -- python bench.py --steps 20 --warmup 10 --no-cpu-baseline --no-other-modes --no-roofline --no-fresh-batches > gpurun_out/prof/${TAG}z.log 2>&1
 O=gpurun_out/bench_$TAG
-python bench.py --steps 30 --warmup 10 2>$O/headline.err | tail -1 > $O/headline.json
+python bench.py --full --steps 30 --warmup 10 2>$O/headline.err | tail -1 > $O/headline.json
 Q="--no-cpu-baseline --no-roofline --no-fresh-batches --no-side-workloads"
 python bench.py --with-optimizer $Q --no-other-modes 2>/dev/null | tail -1 > $O/with_optimizer.json
 python bench.py --workload mp $Q --no-other-modes 2>/dev/null | tail -1 > $O/mp.json
@@ -23,8 +23,8 @@ for b in 64 128; do
 done
 python bench.py --ragged $Q --no-other-modes 2>/dev/null | tail -1 > $O/ragged.json
 python bench.py --batch 38 $Q --no-other-modes 2>/dev/null | tail -1 > $O/batch_38.json
-for b in 32 64 128; do python bench.py --batch $b --steps 12 --warmup 4 $Q 2>/dev/null | tail -1 > $O/batch_$b.json; done
-LOTUS_FORCE_COLLECTIVES=1 python bench.py $Q --no-other-modes 2>/dev/null | tail -1 > $O/one_rank_rccl.json
-LOTUS_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 2 $Q --no-other-modes 2>/dev/null | tail -1 > $O/two_ranks_one_gpu_gloo.json
+for b in 32 64 128; do python bench.py --full --batch $b --steps 12 --warmup 4 $Q 2>/dev/null | tail -1 > $O/batch_$b.json; done
+LOTUS_FORCE_COLLECTIVES=1 python bench.py --full $Q --no-other-modes 2>/dev/null | tail -1 > $O/one_rank_rccl.json
+LOTUS_DIST_BACKEND=gloo python bench.py --full --gpus 2 --steps 5 --warmup 2 $Q --no-other-modes 2>/dev/null | tail -1 > $O/two_ranks_one_gpu_gloo.json
 sha256sum robot-3dlotus_amd/csrc/liblotus_hip.so | cut -c1-16 > $O/so.sha
 ls -la $O

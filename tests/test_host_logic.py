@@ -564,3 +564,17 @@ def test_bench_watchdog_ends_a_rank_that_stopped_ticking():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, cwd=root)
     assert r.returncode == 17, (r.returncode, r.stderr[-2000:])
     assert "still here" in r.stdout and "rank 3 made no progress" in r.stderr and "last stage: alive" in r.stderr
+
+
+def test_bench_gemm_report_needs_full():
+    """bench.py --gemm-report extends the roofline figure, which only --full measures: asked for in a plain run (or with
+    --no-roofline) it is refused before anything is set up, instead of silently writing no report."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for extra in ([], ["--full", "--no-roofline"]):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gemm-report", os.devnull] + extra,
+                           capture_output=True, text=True, timeout=120, cwd=root)
+        assert r.returncode == 2 and "--gemm-report" in r.stderr and "--full" in r.stderr, (extra, r.returncode, r.stderr[-2000:])
+        assert not r.stdout.strip(), r.stdout[-2000:]

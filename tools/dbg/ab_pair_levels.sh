@@ -16,5 +16,5 @@ done
 for v in 0 auto; do if [ $v = 0 ]; then export LOTUS_PAIR=0; else unset LOTUS_PAIR; fi; echo "host floor pair=$v: $(python tools/host_floor.py 2>/dev/null | grep 'host ' | head -1)"; done
 } > gpurun_out/ab_pair_levels2.txt 2>&1
 cat gpurun_out/ab_pair_levels2.txt
-mkdir -p gpurun_out/hl; for i in 1 2 3; do python bench.py --steps 30 --warmup 10 2>gpurun_out/hl/h$i.err | tail -1 > gpurun_out/hl/h$i.json; python -c "
-import json; d=json.load(open('gpurun_out/hl/h$i.json')); print(d['value'], d['ms_per_step'], d['host_ms_per_step'], d['roofline']['frac'], d['roofline']['traffic'])"; done
+for i in 1 2 3; do python bench.py --full --steps 30 --warmup 10 2>/dev/null | tail -1 | python -c "
+import json, sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['host_ms_per_step'], d['roofline']['frac'], d['roofline']['traffic'])"; done

@@ -34,8 +34,8 @@ REPS=20 bash tools/dbg/dp_rehearsal_dist.sh > /dev/null 2>&1; cp gpurun_out/dp_r
 bash tools/dbg/dp_parts.sh > /dev/null 2>&1; cp gpurun_out/dp_parts.txt profiles/${TAG}_dp_parts.txt
 LOTUS_FORCE_COLLECTIVES=1 bash tools/dbg/timeline_cfg.sh rehearsal > /dev/null 2>&1; head -60 gpurun_out/seq_rehearsal.txt | cut -c1-160 > profiles/${TAG}_rehearsal_sequence.txt
 LOTUS_FORCE_COLLECTIVES=1 CENSUS_ARGS="" bash tools/dbg/hip_api_census.sh 2>&1 | cut -c1-160 > profiles/${TAG}_rehearsal_hip_api_census.txt
-python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-other-modes --no-fresh-batches --no-side-workloads --gemm-report profiles/${TAG}_gemm_report.txt > /dev/null 2>&1
-LOTUS_GEMM_DMA=0 python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-other-modes --no-fresh-batches --no-side-workloads --gemm-report profiles/${TAG}_gemm_report_dma_off.txt > /dev/null 2>&1
+python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-other-modes --no-fresh-batches --no-side-workloads --gemm-report profiles/${TAG}_gemm_report.txt > /dev/null 2>&1
+LOTUS_GEMM_DMA=0 python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-other-modes --no-fresh-batches --no-side-workloads --gemm-report profiles/${TAG}_gemm_report_dma_off.txt > /dev/null 2>&1
 mkdir -p gpurun_out/profiles_$TAG
 cp profiles/${TAG}* gpurun_out/profiles_$TAG/ 2>/dev/null
 cp gpurun_out/parity_ledger.json gpurun_out/profiles_$TAG/${TAG}_parity.json 2>/dev/null
