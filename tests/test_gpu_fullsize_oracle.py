@@ -48,7 +48,7 @@ def _dev_batch(batch):
             for k, v in batch.items()}
 
 
-def _run(variant, augment, seed, tag):
+def _run(variant, augment, seed, tag, clouds=16):
     import robot_3dlotus_amd  # noqa: F401
     from oracle.model import Oracle
     from robot_3dlotus_amd import config as lcfg, synth
@@ -57,7 +57,7 @@ def _run(variant, augment, seed, tag):
 
     cfg = lcfg.preset("v1")
     sd = seeded_state_dict(gu.state_template(cfg), seed, variant)
-    batch = synth.synth_batch(16, 4096, seed=seed)
+    batch = synth.synth_batch(clouds, 4096, seed=seed)
     if augment:
         batch = synth.augment_clouds(batch, seed=seed + 1)
     torch.set_num_threads(min(32, torch.get_num_threads() if torch.get_num_threads() > 1 else 16))
@@ -199,3 +199,85 @@ def test_fullsize_v1_against_oracle_scaled_weights():
 
 def test_fullsize_v1_against_oracle_duplicate_voxels():
     _run("scaled", True, 13, "v1_16x4096_scaled_augmented")
+
+
+def test_fullsize_v1_against_oracle_38_clouds():
+    """The headline batch of the published throughput figures (38 clouds x 4096 = 155 648 points): forward, losses, every
+    gradient and the injected-routing proof under the bars of the 16-cloud cases (they are relative per tensor).  Level 0 is past
+    the first segment of the radix histogram scan and the first round of the pooling carry."""
+    _run("scaled", False, 14, "v1_38x4096_scaled", clouds=38)
+
+
+def _hip_model(cfg, sd):
+    from robot_3dlotus_amd.policy import SimplePolicyPTV3CA
+
+    m = SimplePolicyPTV3CA(cfg)
+    m.load_state_dict(sd, strict=True)
+    m = m.cuda().train()
+    m.ptv3_model.proj_drop = m.ptv3_model.attn_drop = 0.0
+    m.act_proj_head.dropout = 0.0
+    m.ptv3_model.order_perms = PERMS
+    return m
+
+
+def _grads_of_one_step(m, dev_batch):
+    for p in m.parameters():
+        p.grad = None
+    _, losses = m(dev_batch, compute_loss=True, compute_final_action=False)
+    losses["total"].backward()
+    torch.cuda.synchronize()
+    return {name: p.grad.clone() for name, p in m.named_parameters()}, losses
+
+
+@pytest.mark.parametrize("clouds", [64, 128])
+def test_fullsize_v1_forward_against_oracle(clouds):
+    """64 and 128 clouds x 4096 points (262 144 / 524 288 rows at level 0), train mode, dropout 0, injected permutations.
+    Forward: logits and the four losses against the float64 oracle (run without autograd: its backward does not fit the host
+    at these sizes) under the bars of _run.  Backward, two properties that need no oracle: two runs give bit-identical
+    gradients, and every gradient is finite and non-zero wherever it is non-zero at 16 clouds."""
+    import robot_3dlotus_amd  # noqa: F401
+    from oracle.model import Oracle
+    from robot_3dlotus_amd import config as lcfg, synth
+    from weights_util import seeded_state_dict
+
+    cfg = lcfg.preset("v1")
+    sd = seeded_state_dict(gu.state_template(cfg), 15, "scaled")
+    batch = synth.synth_batch(clouds, 4096, seed=clouds)
+    torch.set_num_threads(min(32, torch.get_num_threads() if torch.get_num_threads() > 1 else 16))
+    with torch.no_grad():
+        sd64 = {k: (v.clone().double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+        out = Oracle(sd64, lcfg.plain(cfg), training=True, dtype=torch.float64).forward(batch, PERMS)
+    m = _hip_model(cfg, sd)
+    g1, losses = _grads_of_one_step(m, _dev_batch(batch))
+    rec, fails = {"points": int(sum(batch["npoints_in_batch"])), "weights": "scaled",
+                  "yardstick": "oracle/model.py evaluated in float64 under torch.no_grad()"}, []
+    for name, got, ref in (("xt", m.last_pred[0], out["xt"]), ("xr", m.last_pred[1], out["xr"]), ("xo", m.last_pred[2], out["xo"])):
+        ref = ref.detach().numpy()
+        err = float(np.abs(got.detach().cpu().double().numpy() - ref).max())
+        mag = float(np.abs(ref).max())
+        rec["logit_abs_err_" + name], rec["logit_max_" + name] = err, mag
+        if err > LOGIT_TOL * max(1.0, mag):
+            fails.append(f"{name}: max |diff| {err:.3e} (|logit|max {mag:.3g})")
+    for k in ("pos", "rot", "open", "total"):
+        ref = float(out["losses"][k].detach())
+        err = abs(losses[k].item() - ref)
+        rec["loss_abs_err_" + k] = err
+        if err > 1e-4 * max(1.0, abs(ref)):
+            fails.append(f"loss {k}: {losses[k].item()} vs {ref}")
+    del out
+    # backward: bit-identical when repeated
+    g2, _ = _grads_of_one_step(m, _dev_batch(batch))
+    differ = [n for n in g1 if not torch.equal(g1[n], g2[n])]
+    rec["n_gradients"], rec["n_gradients_not_bit_identical"] = len(g1), len(differ)
+    if differ:
+        fails.append(f"{len(differ)} gradients differ between two runs, e.g. {differ[:3]}")
+    # ... finite, and non-zero wherever the 16-cloud step has a non-zero gradient
+    g16, _ = _grads_of_one_step(m, _dev_batch(synth.synth_batch(16, 4096, seed=clouds + 1)))
+    bad = [n for n in g1 if not bool(torch.isfinite(g1[n]).all())]
+    dead = [n for n in g1 if bool((g16[n] != 0).any()) and not bool((g1[n] != 0).any())]
+    rec["n_gradients_nonzero_at_16_clouds"] = sum(1 for n in g16 if bool((g16[n] != 0).any()))
+    rec["n_gradients_not_finite"], rec["n_gradients_dead"] = len(bad), len(dead)
+    if bad or dead:
+        fails.append(f"gradients not finite: {bad[:3]}; zero but non-zero at 16 clouds: {dead[:3]}")
+    ledger.record(f"fullsize_oracle/v1_{clouds}x4096_forward", **rec)
+    assert not fails, "; ".join(fails[:8])

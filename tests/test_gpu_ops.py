@@ -31,7 +31,10 @@ def _close(a, b, tol, msg=""):
                                    (65536, 90, 128), (16, 217, 128), (7, 128, 128), (4097, 128, 512),
                                    # tall thin layers of level 0: the weights-stationary kernel (all four column counts,
                                    # all three reduction depths, a ragged last row tile)
-                                   (65536, 256, 64), (65536, 64, 256), (40011, 128, 128), (65536, 192, 64), (33000, 256, 128)])
+                                   (65536, 256, 64), (65536, 64, 256), (40011, 128, 128), (65536, 192, 64), (33000, 256, 128),
+                                   # 128 clouds x 4096 points at level 0 and 64 clouds at level 1: operands of 0.1-0.5 GB behind the
+                                   # 32-bit byte offsets and clamped buffer descriptors of the tile loads
+                                   (524288, 192, 64), (524288, 64, 256), (185085, 384, 128)])
 @pytest.mark.parametrize("act", [0, 1, 2])
 def test_linear_fwd(M, N, K, act):
     ops = _ops()
@@ -45,7 +48,8 @@ def test_linear_fwd(M, N, K, act):
 
 
 @pytest.mark.parametrize("M,N,K", [(65536, 256, 64), (1000, 64, 192), (441, 3072, 768), (65536, 90, 128), (16, 217, 128),
-                                   (65536, 64, 256), (40011, 128, 128), (65536, 64, 192)])
+                                   (65536, 64, 256), (40011, 128, 128), (65536, 64, 192),
+                                   (524288, 192, 64), (524288, 64, 256), (185085, 384, 128)])
 def test_linear_dgrad_wgrad(M, N, K):
     ops = _ops()
     g = torch.Generator().manual_seed(M * 3 + N + K)
@@ -122,7 +126,7 @@ def test_linear_dropout_statistics_and_replay():
 
 
 # ------------------------------------------------------------------------------------ norms
-@pytest.mark.parametrize("M,C", [(65536, 64), (1000, 128), (777, 256), (441, 512), (300, 768)])
+@pytest.mark.parametrize("M,C", [(65536, 64), (1000, 128), (777, 256), (441, 512), (300, 768), (524288, 64)])
 def test_layernorm(M, C):
     ops = _ops()
     g = torch.Generator().manual_seed(C)
@@ -140,7 +144,7 @@ def test_layernorm(M, C):
     _close(db, bd.grad, 5e-6, "ln dbeta")
 
 
-@pytest.mark.parametrize("M,C", [(65536, 64), (6921, 256), (37, 768)])
+@pytest.mark.parametrize("M,C", [(65536, 64), (6921, 256), (37, 768), (524288, 64)])
 @pytest.mark.parametrize("training", [True, False])
 def test_batchnorm_gelu(M, C, training):
     ops = _ops()
@@ -213,6 +217,51 @@ def test_subm_conv_fwd_dgrad_wgrad(cin, cout, k):
     if k == 3:
         dx = ops.conv_dgrad(dy.cuda(), w.cuda(), nbr, got[0].order[0], w_t=wt)
         _close(dx, xd.grad, 3e-6, "conv dgrad (pair-compacted, packed weights)")
+
+
+@pytest.mark.parametrize("path", ["tap_plan", "pairs"])
+def test_subm_conv_level0_of_64_clouds(path):
+    """The 3^3 convolution at 64 channels over level 0 of 64 clouds x 4096 points (262 144 rows, 1.8 GB of per-tap partial
+    sums on the tap-plan path): forward, input gradient and weight gradient against the float64 expression of
+    spconv.SubMConv3d (model.py:615-622), on the tap-grouped path and on the pair-compacted one."""
+    import robot_3dlotus_amd  # noqa: F401
+    from robot_3dlotus_amd import synth
+    from robot_3dlotus_amd._capi import query
+    from robot_3dlotus_amd.frontend import FrontEnd
+
+    ops = _ops()
+    C = 64
+    batch = synth.synth_batch(64, 4096, seed=17)
+    L = FrontEnd(2, conv_widths=[C, C]).build(batch["pc_fts"].cuda(), batch["npoints_in_batch"], batch["txt_lens"], [[0, 1, 2, 3]] * 2)[0]
+    n = L.n
+    assert n == 262144 and query("lotus_conv_tap_eligible", n, C, C) == 1 and L.tap_plan is not None
+    grid = fe.grid_coord(batch["pc_fts"][:, :3].numpy())
+    nbr_ref = fe.neighbour_table(grid, fe.offset2batch(batch["npoints_in_batch"]), 3)
+    np.testing.assert_array_equal(L.nbr27.cpu().numpy().T, nbr_ref)
+    g = torch.Generator().manual_seed(C)
+    x, dy = torch.randn(n, C, generator=g), torch.randn(n, C, generator=g)
+    w = torch.randn(C, 3, 3, 3, C, generator=g) / (C * 9) ** 0.5
+    b, add = torch.randn(C, generator=g), torch.randn(n, C, generator=g)
+    nb, w64 = torch.from_numpy(nbr_ref.T.copy()).long(), w.double().reshape(C, 27, C)
+    yr, dr, dwr = b.double()[None, :] + add.double(), add.double().clone(), torch.zeros(C, 27, C, dtype=torch.float64)
+    for t in range(27):
+        m = nb[t] >= 0
+        xg = x.double()[nb[t][m]]
+        yr[m] += xg @ w64[:, t, :].T
+        dr.index_add_(0, nb[t][m], dy.double()[m] @ w64[:, t, :])     # dx[nbr] += dy W_t (transposed pair list)
+        dwr[:, t, :] = dy.double()[m].T @ xg
+    xc, dyc, wc = x.cuda(), dy.cuda(), w.cuda()
+    wt = ops.conv_weight_t(wc)
+    plan = L.tap_plan if path == "tap_plan" else None
+    y = ops.conv_fwd(xc, wc, b.cuda(), L.nbr27, L.order[0], add=add.cuda(), w_t=wt, tap_plan=plan)
+    _close(y, yr, 3e-6, "conv fwd")
+    d = ops.conv_dgrad(dyc, wc, L.nbr27, L.order[0], add=add.cuda(), w_t=wt, lvl=L, tap_plan=plan)
+    _close(d, dr, 3e-6, "conv dgrad")
+    dw, db = ops.conv_wgrad(dyc, xc, w.shape, L.nbr27)
+    _close(dw, dwr.reshape(w.shape), 5e-6, "conv wgrad")
+    _close(db, dy.double().sum(0), 5e-6, "conv bgrad")
+    y2 = ops.conv_fwd(xc, wc, b.cuda(), L.nbr27, L.order[0], add=add.cuda(), w_t=wt, tap_plan=plan)
+    assert torch.equal(y, y2)   # deterministic
 
 
 def _dup_cloud_levels(seed):

@@ -340,7 +340,7 @@ def test_tap_grouped_convolution_of_every_level():
     """lotus_subm_conv with a tap plan (27 gathered dense products + fixed-order tap sum; round 4: the deep levels, round 5:
     every level from 64 channels up, on the LDS-DMA tiles — 64-wide and 128-wide tile shapes, ragged last tiles): the plan is a permutation-free compaction of the neighbour table, and forward / input gradient agree with the
     float64 expression of spconv.SubMConv3d (model.py:615-622) and with the pair-compacted kernel."""
-    import numpy as np
+    from frontend_util import check_tap_plan
     from robot_3dlotus_amd import ops, synth
     from robot_3dlotus_amd.frontend import FrontEnd
     from robot_3dlotus_amd._capi import query
@@ -351,16 +351,7 @@ def test_tap_grouped_convolution_of_every_level():
     for li, C in ((0, 64), (1, 128), (2, 256), (3, 512)):
         L = levels[li]
         assert query("lotus_conv_tap_eligible", L.n, C, C) == 1 and L.tap_plan is not None
-        n64 = (L.n + 63) // 64 * 64
-        plan = L.tap_plan.cpu().numpy()
-        cnt, tin, pos = plan[:27], plan[32:32 + 27 * n64].reshape(27, n64), plan[32 + 27 * n64:].reshape(27, L.n)
-        nbr = L.nbr27.cpu().numpy()
-        np.testing.assert_array_equal(cnt, (nbr >= 0).sum(1))
-        for t in range(27):
-            rows = np.nonzero(pos[t] >= 0)[0]
-            assert len(rows) == cnt[t] and set(pos[t][rows] - t * n64) == set(range(cnt[t]))
-            np.testing.assert_array_equal(tin[t][pos[t][rows] - t * n64], nbr[t][rows])   # the pair (row, neighbour) survives
-            assert (tin[t][cnt[t]:(cnt[t] + 63) // 64 * 64] == 0).all()                      # padding gathers a valid row
+        check_tap_plan(L.tap_plan.cpu().numpy(), L.nbr27.cpu().numpy(), L.n, L.order[0].cpu().numpy())
         torch.manual_seed(li)
         x = torch.randn(L.n, C, device=dev)
         w = torch.randn(C, 3, 3, 3, C, device=dev) / (C * 9) ** 0.5
