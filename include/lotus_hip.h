@@ -558,6 +558,26 @@ int lotus_adabn_apply(const float* x, const float* mean, const float* invstd, co
 int lotus_adabn_bwd(const float* dy, const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
                     const float* mod, int mod_ld, const int* off, int B, float* dx, float* dgamma, float* dbeta, float* dmod,
                     int dmod_ld, int M, int C, int act, int training, void* workspace, size_t workspace_bytes, void* stream);
+/* The same two passes split for SyncBatchNorm (nn.SyncBatchNorm.convert_sync_batchnorm under DistributedDataParallel,
+ * genrobo3d/train/train_simple_policy.py:116-117,177; PDNorm.norm is the converted layer, model.py:273-274): statistics -> one fp64
+ * message double[2C + 1], SUM all-reduced across ranks by the caller -> apply.  A cloud lives on one rank, so dmod and the LOCAL
+ * dgamma / dbeta are final after the statistics half; only the two column sums of the BatchNorm backward cross ranks.
+ *   forward message  (sum x, sum x^2, rows): lotus_batchnorm_stats_fused(mean = invstd = NULL), then lotus_adabn_apply_sums, which
+ *     finishes mean / invstd (outputs, saved for backward) and the running averages (NULL = not tracked; unbiased variance with the
+ *     global row count) in the launch that applies them; M == 0 still finishes the statistics;
+ *   backward message (sum dxhat, sum dxhat xhat, rows) = (gamma dbeta, gamma dgamma, M), dxhat_i = dz_i (1 + scale_b(i)) gamma:
+ *     lotus_adabn_bwd_stats writes dgamma, dbeta, dmod and the local message (fixed-order sums, products formed in fp64),
+ *     lotus_adabn_bwd_apply_sums: dx_i = invstd (dxhat_i - sums[0..C) / sums[2C] - xhat_i sums[C..2C) / sums[2C]). */
+int lotus_adabn_apply_sums(const float* x, const double* sums, const float* gamma, const float* beta, const float* mod, int mod_ld,
+                           const int* off, int B, float* y, float* mean, float* invstd, float* running_mean, float* running_var,
+                           int M, int C, int act, float eps, float momentum, void* stream);
+int lotus_adabn_bwd_stats(const float* dy, const float* x, const float* mean, const float* invstd, const float* gamma,
+                          const float* beta, const float* mod, int mod_ld, const int* off, int B, float* dgamma, float* dbeta,
+                          float* dmod, int dmod_ld, double* sums, int M, int C, int act, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int lotus_adabn_bwd_apply_sums(const float* dy, const float* x, const float* mean, const float* invstd, const float* gamma,
+                               const float* beta, const float* mod, int mod_ld, const int* off, int B, const double* sums, float* dx,
+                               int M, int C, int act, void* stream);
 /* PDNorm.modulation[0] = nn.SiLU (model.py:276-278): y = SiLU(x), or y = dy SiLU'(x) when dy is given */
 int lotus_ada_silu(const float* x, const float* dy, float* y, int n, void* stream);
 

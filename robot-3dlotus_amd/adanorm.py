@@ -6,7 +6,9 @@ LayerNorm at `cpe.2`, `norm1` and `norm2` of every Block.  Norm j of width C is 
 [shift_j | scale_j] = Linear_j(SiLU(c_b)), c_b the instruction (+ pose, + step) context of cloud b.
 
 The autograd nodes below are composed of the library's existing per-launch primitives (sparse convolution, dense layers,
-patch attention, BatchNorm statistics) and the modulated-norm entry points of csrc/adanorm.hip.  All modulation projections
+patch attention, BatchNorm statistics) and the modulated-norm entry points of csrc/adanorm.hip.  Under data parallel
+(parallel.GradReducer + parallel.enable_sync_batchnorm) the 13 BatchNorm sites of a five-stage model run split — statistics ->
+one fp64 message per site and direction (the two unpooling branches share theirs: 9 forward + 9 backward) -> apply.  All modulation projections
 of a forward pass are one product (ModAllFn; the same idea as ops.KvAllFn for the CABlocks): SiLU(c) [B, 256] against the
 concatenated weights of every PDNorm, and one weight-gradient / one input-gradient product in backward over the d mod slab
 that the norms' backward passes fill in place.  fp32 activation storage only.
@@ -52,9 +54,32 @@ def adaln_bwd(dy, x, mean, rstd, g, b, mod, dmod, lvl, add=None):
     return dx, dg, db
 
 
-def adabn_fwd(x, g, b, rmean, rvar, mod, lvl, training, act=ACT_GELU):
-    """act((BN(x) g + b) (1 + scale_b) + shift_b): batch statistics (+ running-average update) in training, running ones in eval."""
+def _split():
+    """SyncBatchNorm route (statistics -> ops.BnState.reduce -> apply) of the BatchNorm sites: a training pass while a statistics
+    hook is installed (parallel.enable_sync_batchnorm)."""
+    return ops.BnState.reduce is not None
+
+
+def _adabn_apply_sums(x, sums, g, b, rmean, rvar, mod, lvl, act):
+    """Second half of the split forward: mean / invstd / running averages from the all-reduced sums and the modulated apply pass."""
     M, C = x.shape
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    invstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    y = torch.empty_like(x)
+    call("lotus_adabn_apply_sums", x, sums, g, b, mod, mod.stride(0), lvl.off, _n_clouds(lvl), y, mean, invstd, rmean, rvar, M, C, act,
+         float(BN_EPS), float(BN_MOMENTUM))
+    return y, mean, invstd
+
+
+def adabn_fwd(x, g, b, rmean, rvar, mod, lvl, training, act=ACT_GELU):
+    """act((BN(x) g + b) (1 + scale_b) + shift_b): batch statistics (+ running-average update) in training, running ones in eval.
+    With a statistics hook (SyncBatchNorm) the training pass is statistics -> one fp64 message (sum x, sum x^2, rows) -> apply."""
+    M, C = x.shape
+    if training and _split():
+        sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
+        ops._bn_stats(x, sums)
+        ops.BnState.reduce(sums)
+        return _adabn_apply_sums(x, sums, g, b, rmean, rvar, mod, lvl, act)
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     invstd = torch.empty(C, dtype=torch.float32, device=x.device)
     if training:
@@ -69,8 +94,46 @@ def adabn_fwd(x, g, b, rmean, rvar, mod, lvl, training, act=ACT_GELU):
     return y, mean, invstd
 
 
+def adabn_fwd_pair(xa, pa, xb, pb, training, act=ACT_GELU):
+    """Two independent sites (the branches of SerializedUnpooling) with ONE statistics message when SyncBatchNorm is on — the
+    adaptive ops.bn_fwd_pair.  pa / pb = (g, b, rmean, rvar, mod, lvl)."""
+    if not training or not _split():
+        return adabn_fwd(xa, *pa, training, act), adabn_fwd(xb, *pb, training, act)
+    na = 2 * xa.shape[1] + 1
+    sums = torch.empty(na + 2 * xb.shape[1] + 1, dtype=torch.float64, device=xa.device)
+    ops._bn_stats(xa, sums[:na])
+    ops._bn_stats(xb, sums[na:])
+    ops.BnState.reduce(sums)
+    return _adabn_apply_sums(xa, sums[:na], *pa, act), _adabn_apply_sums(xb, sums[na:], *pb, act)
+
+
+def _adabn_bwd_stats(dy, x, mean, invstd, g, b, mod, dmod, lvl, act, sums):
+    """First half of the split backward: dgamma, dbeta (LOCAL sums: averaging them is the reducer's job), d mod into `dmod`, and the
+    local message sums = (gamma dbeta, gamma dgamma, rows) in fp64."""
+    M, C = x.shape
+    B = _n_clouds(lvl)
+    dg = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    ws = WS.get(query("lotus_adanorm_workspace", M, B, C), x.device, slot=_WS_SLOT)
+    call("lotus_adabn_bwd_stats", dy, x, mean, invstd, g, b, mod, mod.stride(0), lvl.off, B, dg, db, dmod, dmod.stride(0), sums, M, C,
+         act, ws, ws.numel())
+    return dg, db
+
+
+def _adabn_bwd_apply_sums(dy, x, mean, invstd, g, b, mod, lvl, act, sums):
+    M, C = x.shape
+    dx = torch.empty_like(x)
+    call("lotus_adabn_bwd_apply_sums", dy, x, mean, invstd, g, b, mod, mod.stride(0), lvl.off, _n_clouds(lvl), sums, dx, M, C, act)
+    return dx
+
+
 def adabn_bwd(dy, x, mean, invstd, g, b, mod, dmod, lvl, training, act=ACT_GELU):
     M, C = x.shape
+    if training and _split():  # partials + fixed-order reduce -> message (sum dxhat, sum dxhat xhat, rows) -> apply
+        sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
+        dg, db = _adabn_bwd_stats(dy, x, mean, invstd, g, b, mod, dmod, lvl, act, sums)
+        ops.BnState.reduce(sums)
+        return _adabn_bwd_apply_sums(dy, x, mean, invstd, g, b, mod, lvl, act, sums), dg, db
     B = _n_clouds(lvl)
     dx = torch.empty_like(x)
     dg = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -79,6 +142,21 @@ def adabn_bwd(dy, x, mean, invstd, g, b, mod, dmod, lvl, training, act=ACT_GELU)
     call("lotus_adabn_bwd", dy, x, mean, invstd, g, b, mod, mod.stride(0), lvl.off, B, dx, dg, db, dmod, dmod.stride(0), M, C, act,
          1 if training else 0, ws, ws.numel())
     return dx, dg, db
+
+
+def adabn_bwd_pair(a, bb, training, act=ACT_GELU):
+    """Backward of adabn_fwd_pair: a / bb = (dy, x, mean, invstd, g, b, mod, dmod, lvl); one statistics message for both."""
+    if not training or not _split():
+        return adabn_bwd(*a, training, act), adabn_bwd(*bb, training, act)
+    na = 2 * a[1].shape[1] + 1
+    sums = torch.empty(na + 2 * bb[1].shape[1] + 1, dtype=torch.float64, device=a[1].device)
+    sa, sb = sums[:na], sums[na:]
+    ga = _adabn_bwd_stats(*a, act, sa)
+    gb = _adabn_bwd_stats(*bb, act, sb)
+    ops.BnState.reduce(sums)
+    da = _adabn_bwd_apply_sums(*a[:7], a[8], act, sa)
+    db_ = _adabn_bwd_apply_sums(*bb[:7], bb[8], act, sb)
+    return (da,) + ga, (db_,) + gb
 
 
 def silu(x, dy=None):
@@ -316,8 +394,8 @@ class AdaUnpoolFn(torch.autograd.Function):
                 ju, js):
         lu, _ = ops.linear_fwd(xc, wu, bu)
         ls, _ = ops.linear_fwd(xp, ws_, bs)
-        up, mu, iu = adabn_fwd(lu, gu, betau, rmu, rvu, modu, child, training)
-        skip, ms, is_ = adabn_fwd(ls, gs, betas, rms, rvs, mods, lvl, training)
+        (up, mu, iu), (skip, ms, is_) = adabn_fwd_pair(lu, (gu, betau, rmu, rvu, modu, child), ls, (gs, betas, rms, rvs, mods, lvl),
+                                                       training)
         x = torch.empty_like(skip)
         call("lotus_unpool_fwd", skip, up, child.cluster, skip.shape[0], skip.shape[1], x)
         ctx.meta = (child, lvl, training, bank, ju, js)
@@ -334,8 +412,8 @@ class AdaUnpoolFn(torch.autograd.Function):
         call("lotus_unpool_bwd", dx, child.members, child.seg_start, child.n, C, dup)
         dsk = ops.add(dx, dskip.contiguous()) if dskip is not None else dx
         dmu, dms = bank.grad_slice(ju), bank.grad_slice(js)
-        dlu, dgu, dbetau = adabn_bwd(dup, lu, mu, iu, gu, betau, modu, dmu, child, training)
-        dls, dgs, dbetas = adabn_bwd(dsk, ls, ms, is_, gs, betas, mods, dms, lvl, training)
+        (dlu, dgu, dbetau), (dls, dgs, dbetas) = adabn_bwd_pair((dup, lu, mu, iu, gu, betau, modu, dmu, child),
+                                                                (dsk, ls, ms, is_, gs, betas, mods, dms, lvl), training)
         dwu, dbu = ops.linear_wgrad(dlu, xc)
         dxc = ops.linear_dgrad(dlu, wu)
         dws, dbs = ops.linear_wgrad(dls, xp)
@@ -504,12 +582,19 @@ class PointTransformerV3AdaNorm(PointTransformerV3CA):
         self.register_load_state_dict_post_hook(lambda m, _keys: setattr(m, "_step", None))
 
     def _check_sync_bn(self):
-        """SyncBatchNorm under modulation (its backward across ranks) is not built: refuse data-parallel runs instead of
-        normalising per rank."""
+        """Data parallel (train_simple_policy.py:116-117,177): BatchNorm containers converted by
+        `nn.SyncBatchNorm.convert_sync_batchnorm` switch the statistics messages on (parallel.enable_sync_batchnorm — collective:
+        every rank enters its first forward), as PointTransformerV3CA does.  A process group of more than one rank with neither
+        converted containers nor a statistics hook would normalise per rank, which is not what the reference trains: refused."""
         import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise NotImplementedError("SimplePolicyPTV3AdaNorm runs on one process: a process group with world size "
-                                      f"{dist.get_world_size()} > 1 (SyncBatchNorm under PDNorm modulation) is not supported")
+        if ops.BnState.reduce is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            if not any(isinstance(m, nn.SyncBatchNorm) for m in self.modules()):
+                raise NotImplementedError(
+                    f"SimplePolicyPTV3AdaNorm in a process group with world size {dist.get_world_size()} > 1 needs SyncBatchNorm "
+                    "statistics: convert the model with nn.SyncBatchNorm.convert_sync_batchnorm(model) or call "
+                    "parallel.enable_sync_batchnorm() before the first forward (BatchNorm per rank is not built)")
+            from . import parallel
+            parallel.enable_sync_batchnorm()
         self._sync_bn_checked = True
 
     def _mod_params(self):

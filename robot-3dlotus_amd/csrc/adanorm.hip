@@ -8,6 +8,10 @@
 // and the BatchNorm backward's column sums are sum dxhat = gamma dbeta, sum dxhat xhat = gamma dgamma.  The sums come from a
 // grid over (cloud, row chunk) — a block never straddles two clouds — whose per-block partials a second small kernel adds in
 // fixed order: no atomics, bit-reproducible.  fp32 activations only (no bf16-storage twin).
+// SyncBatchNorm (data parallel): a BN site runs statistics -> message -> apply with one fp64 message double[2C + 1] per direction,
+// SUM all-reduced by the caller: forward (sum x, sum x^2, rows) from lotus_batchnorm_stats_fused, finished by
+// lotus_adabn_apply_sums; backward (sum dxhat, sum dxhat xhat, rows) = (gamma dbeta, gamma dgamma, M) from lotus_adabn_bwd_stats —
+// a cloud lives on one rank, so dmod and the LOCAL dgamma / dbeta are final there — consumed by lotus_adabn_bwd_apply_sums.
 #include "common.h"
 
 namespace LOTUS_NS {
@@ -211,6 +215,15 @@ struct AdaBnP {
   float* y;  // forward: y; backward apply: dx
   float* part;
   int M, C, B, ld, G, act, training;
+  // the split (SyncBatchNorm) passes, adabn_cols_kernel: `sums` is the all-reduced fp64 message.  Forward: (sum x, sum x^2, rows)
+  // -> mean / invstd (written to out_mean / out_invstd for backward) and the running averages; backward: (sum dxhat,
+  // sum dxhat xhat, rows) of ALL ranks.
+  const double* sums;
+  float* out_mean;
+  float* out_invstd;
+  float* running_mean;
+  float* running_var;
+  float eps, momentum;
 };
 
 // BatchNorm backward partials: dz = dy act'((xhat gamma + beta)(1 + s) + shift), P += dz xhat, Q += dz over the chunk
@@ -269,14 +282,20 @@ __global__ __launch_bounds__(256) void adabn_part_kernel(AdaBnP p) {
 
 // Fixed-order reduction of the (P, Q) partials: dmod[b] = (Q_b, gamma P_b + beta Q_b), dgamma = sum_b (1 + s_b) P_b,
 // dbeta = sum_b (1 + s_b) Q_b.  Block = 64 columns x 4 cloud lanes (cloud lane t takes b = t, t + 4, ...), combined in LDS.
+// SUMS (the SyncBatchNorm backward, lotus_adabn_bwd_stats): also the fp64 message sums[2C + 1] = (gamma dbeta, gamma dgamma, M) =
+// (sum dxhat, sum dxhat xhat, rows) of the local rows, products and the sum over clouds formed in double from the fp32 P_b, Q_b.
+template <bool SUMS>
 __global__ __launch_bounds__(256) void ada_param_reduce_kernel(const float* __restrict__ part, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, const float* __restrict__ mod, int ld,
                                                                float* __restrict__ dmod, int dld, float* __restrict__ dgamma,
-                                                               float* __restrict__ dbeta, int B, int G, int C) {
+                                                               float* __restrict__ dbeta, int B, int G, int C,
+                                                               double* __restrict__ sums, int M) {
   __shared__ float red[2][4][64];
+  __shared__ double dred[2][4][64];  // (SUMS only)
   const int cl = threadIdx.x & 63, t = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
   float sg = 0.f, sb = 0.f;
+  double dsg = 0.0, dsb = 0.0;
   if (c < C) {
     const float g = gamma[c], bt = beta[c];
     for (int b = t; b < B; b += 4) {
@@ -289,17 +308,32 @@ __global__ __launch_bounds__(256) void ada_param_reduce_kernel(const float* __re
       const float s1 = 1.f + mod[(long)b * ld + C + c];
       sg += s1 * P;
       sb += s1 * Q;
+      if (SUMS) {
+        const double d1 = 1.0 + (double)mod[(long)b * ld + C + c];
+        dsg += d1 * (double)P;
+        dsb += d1 * (double)Q;
+      }
       dmod[(long)b * dld + c] = Q;
       dmod[(long)b * dld + C + c] = g * P + bt * Q;
     }
   }
   red[0][t][cl] = sg;
   red[1][t][cl] = sb;
+  if (SUMS) {
+    dred[0][t][cl] = dsg;
+    dred[1][t][cl] = dsb;
+  }
   __syncthreads();
   if (t == 0 && c < C) {
     dgamma[c] = ((red[0][0][cl] + red[0][1][cl]) + red[0][2][cl]) + red[0][3][cl];
     dbeta[c] = ((red[1][0][cl] + red[1][1][cl]) + red[1][2][cl]) + red[1][3][cl];
+    if (SUMS) {
+      const double g = (double)gamma[c];
+      sums[c] = g * (((dred[1][0][cl] + dred[1][1][cl]) + dred[1][2][cl]) + dred[1][3][cl]);
+      sums[C + c] = g * (((dred[0][0][cl] + dred[0][1][cl]) + dred[0][2][cl]) + dred[0][3][cl]);
+    }
   }
+  if (SUMS && blockIdx.x == 0 && threadIdx.x == 0) sums[2 * C] = (double)M;
 }
 
 // BatchNorm apply: y = act((xhat gamma + beta)(1 + s_b) + shift_b); backward (p.dy): dx = invstd (dxhat - sum dxhat / M -
@@ -330,6 +364,78 @@ __global__ __launch_bounds__(256) void adabn_apply_kernel(AdaBnP p) {
         const float z = (xh * g4[e] + b4[e]) * (1.f + s4[e]) + h4[e];
         const float dxh = ds[e] * act_grad_f(z, p.act) * (1.f + s4[e]) * g4[e];
         o[e] = p.training ? i4[e] * (dxh - (g4[e] * db4[e]) * inv_m - xh * (g4[e] * dg4[e]) * inv_m) : i4[e] * dxh;
+      }
+    }
+    st4q(p.y, i, make_float4(o[0], o[1], o[2], o[3]));
+  }
+}
+
+// The apply passes of the split BatchNorm (statistics -> message -> apply), forward and backward, from the all-reduced fp64
+// message p.sums.  The launch makes gridDim.x * 256 a multiple of C / 4 (ada_cols_grid), so a thread keeps ONE column quad for its
+// whole grid-stride walk: the column constants — with their fp64 divisions — are formed once per thread, only the cloud's
+// [shift | scale] is looked up per row.  Forward: the arithmetic of bn_finalize_kernel (norm.hip) with the GLOBAL row count; the
+// threads of the first quad row also write mean / invstd for backward and update the running averages (M == 0: nothing else).
+// Backward: dx = invstd (dxhat - S1 / M_all - xhat S2 / M_all), dxhat = dy act'(.) (1 + s_b) gamma.
+__global__ __launch_bounds__(256) void adabn_cols_kernel(AdaBnP p) {
+  LOTUS_T_PRIO();
+  const int c4 = p.C / 4;
+  const long total4 = (long)p.M * c4;
+  const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+  const bool first = !p.dy && i0 < c4;
+  if (i0 >= total4 && !first) return;
+  const int q = (int)(i0 % c4);
+  float m4[4], i4[4], a4[4] = {0.f, 0.f, 0.f, 0.f}, b4m[4] = {0.f, 0.f, 0.f, 0.f};
+  const double count = p.sums[2 * p.C];
+  if (!p.dy) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int c = q * 4 + e;
+      const double m = p.sums[c] / count;
+      double var = p.sums[p.C + c] / count - m * m;
+      if (var < 0) var = 0;
+      m4[e] = (float)m;
+      i4[e] = (float)(1.0 / sqrt(var + (double)p.eps));
+      if (first) {
+        p.out_mean[c] = m4[e];
+        p.out_invstd[c] = i4[e];
+        if (p.running_mean) {
+          const double unbiased = count > 1 ? var * count / (count - 1) : var;
+          p.running_mean[c] = (1.f - p.momentum) * p.running_mean[c] + p.momentum * (float)m;
+          p.running_var[c] = (1.f - p.momentum) * p.running_var[c] + p.momentum * (float)unbiased;
+        }
+      }
+    }
+  } else {
+    const float4 mu = ld4q(p.mean, q), is = ld4q(p.invstd, q);
+    m4[0] = mu.x; m4[1] = mu.y; m4[2] = mu.z; m4[3] = mu.w;
+    i4[0] = is.x; i4[1] = is.y; i4[2] = is.z; i4[3] = is.w;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      a4[e] = (float)(p.sums[q * 4 + e] / count);
+      b4m[e] = (float)(p.sums[p.C + q * 4 + e] / count);
+    }
+  }
+  const float4 gm = ld4q(p.gamma, q), bt = ld4q(p.beta, q);
+  const float g4[4] = {gm.x, gm.y, gm.z, gm.w}, b4[4] = {bt.x, bt.y, bt.z, bt.w};
+  const int drow = (int)(step / c4);  // (the column quad is fixed: a grid step is a whole number of rows)
+  int row = (int)(i0 / c4);
+  for (long i = i0; i < total4; i += step, row += drow) {
+    const float* md = p.mod + (long)ada_cloud(p.off, p.B, row) * p.ld;
+    const float4 xv = ld4q(p.x, i), sh = ld4q(md, q), sc = ld4q(md + p.C, q);
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, h4[4] = {sh.x, sh.y, sh.z, sh.w}, s4[4] = {sc.x, sc.y, sc.z, sc.w};
+    float o[4];
+    if (!p.dy) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = act_f(((xs[e] - m4[e]) * i4[e] * g4[e] + b4[e]) * (1.f + s4[e]) + h4[e], p.act);
+    } else {
+      const float4 dv = ld4q(p.dy, i);
+      const float ds[4] = {dv.x, dv.y, dv.z, dv.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float xh = (xs[e] - m4[e]) * i4[e];
+        const float z = (xh * g4[e] + b4[e]) * (1.f + s4[e]) + h4[e];
+        const float dxh = ds[e] * act_grad_f(z, p.act) * (1.f + s4[e]) * g4[e];
+        o[e] = i4[e] * (dxh - a4[e] - xh * b4m[e]);
       }
     }
     st4q(p.y, i, make_float4(o[0], o[1], o[2], o[3]));
@@ -370,6 +476,15 @@ static int ada_grid(long total4) {
   return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
+// adabn_cols_kernel: ada_grid rounded up to whole column periods (gridDim.x * 256 a multiple of C / 4, and >= C / 4 threads)
+static int ada_cols_grid(long total4, int C) {
+  const int c4 = C / 4;
+  int a = 256, b = c4;
+  while (b) { const int t = a % b; a = b; b = t; }  // a = gcd(256, c4)
+  const int unit = c4 / a;
+  return (ada_grid(total4) + unit - 1) / unit * unit;
+}
+
 }  // namespace LOTUS_NS
 
 using namespace LOTUS_NS;
@@ -405,8 +520,8 @@ int lotus_adaln_bwd(const float* dy, const float* x, const float* mean, const fl
   LOTUS_CHECK_ARG(workspace && workspace_bytes >= lotus_adanorm_workspace(M, B, C), "lotus_adaln_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   LOTUS_LAUNCH(adaln_bwd_kernel, dim3(p.G, B), dim3(256), (size_t)(256 / p.LPR) * 2 * C * sizeof(float), st, p);
-  LOTUS_LAUNCH(ada_param_reduce_kernel, dim3(cdiv(C, 64)), dim3(256), 0, st, p.part, gamma, beta, mod, mod_ld, dmod, dmod_ld,
-               dgamma, dbeta, B, p.G, C);
+  LOTUS_LAUNCH(ada_param_reduce_kernel<false>, dim3(cdiv(C, 64)), dim3(256), 0, st, p.part, gamma, beta, mod, mod_ld, dmod, dmod_ld,
+               dgamma, dbeta, B, p.G, C, (double*)nullptr, M);
   LOTUS_LAUNCH_CHECK("lotus_adaln_bwd");
   return LOTUS_OK;
 }
@@ -439,10 +554,67 @@ int lotus_adabn_bwd(const float* dy, const float* x, const float* mean, const fl
   hipStream_t st = (hipStream_t)stream;
   const int c4 = C / 4, tpr = c4 < 256 ? c4 : 256;
   LOTUS_LAUNCH(adabn_part_kernel, dim3(p.G, B), dim3(256), (size_t)(256 / tpr) * 2 * C * sizeof(float), st, p);
-  LOTUS_LAUNCH(ada_param_reduce_kernel, dim3(cdiv(C, 64)), dim3(256), 0, st, p.part, gamma, beta, mod, mod_ld, dmod, dmod_ld,
-               dgamma, dbeta, B, p.G, C);
+  LOTUS_LAUNCH(ada_param_reduce_kernel<false>, dim3(cdiv(C, 64)), dim3(256), 0, st, p.part, gamma, beta, mod, mod_ld, dmod, dmod_ld,
+               dgamma, dbeta, B, p.G, C, (double*)nullptr, M);
   if (M > 0) LOTUS_LAUNCH(adabn_apply_kernel, dim3(ada_grid((long)M * C / 4)), dim3(256), 0, st, p);
   LOTUS_LAUNCH_CHECK("lotus_adabn_bwd");
+  return LOTUS_OK;
+}
+
+// Forward from the (all-reduced) statistics sums = (sum x, sum x^2, rows): mean / invstd (saved for backward), the running
+// averages and the modulated apply pass in one launch.  M == 0 (an empty shard): the statistics alone.
+int lotus_adabn_apply_sums(const float* x, const double* sums, const float* gamma, const float* beta, const float* mod, int mod_ld,
+                           const int* off, int B, float* y, float* mean, float* invstd, float* running_mean, float* running_var,
+                           int M, int C, int act, float eps, float momentum, void* stream) {
+  LOTUS_CHECK_ARG(sums && gamma && beta && mean && invstd && (!running_mean == !running_var) && M >= 0 && C > 0 && C % 4 == 0 &&
+                  (M == 0 || (x && y && mod && off && B > 0 && mod_ld >= 2 * C)), "lotus_adabn_apply_sums: bad arguments");
+  AdaBnP p;
+  memset(&p, 0, sizeof(p));
+  p.x = x; p.gamma = gamma; p.beta = beta; p.mod = mod; p.off = off; p.y = y;
+  p.M = M; p.C = C; p.B = B; p.ld = mod_ld; p.act = act;
+  p.sums = sums; p.out_mean = mean; p.out_invstd = invstd; p.running_mean = running_mean; p.running_var = running_var;
+  p.eps = eps; p.momentum = momentum;
+  LOTUS_LAUNCH(adabn_cols_kernel, dim3(ada_cols_grid((long)M * C / 4, C)), dim3(256), 0, (hipStream_t)stream, p);
+  LOTUS_LAUNCH_CHECK("lotus_adabn_apply_sums");
+  return LOTUS_OK;
+}
+
+// Backward, first half: the (cloud, chunk) partials and their fixed-order reduction as in lotus_adabn_bwd — dgamma, dbeta (LOCAL
+// sums) and dmod are final — plus the fp64 message sums[2C + 1] = (gamma dbeta, gamma dgamma, M) of the local rows.
+int lotus_adabn_bwd_stats(const float* dy, const float* x, const float* mean, const float* invstd, const float* gamma,
+                          const float* beta, const float* mod, int mod_ld, const int* off, int B, float* dgamma, float* dbeta,
+                          float* dmod, int dmod_ld, double* sums, int M, int C, int act, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  LOTUS_CHECK_ARG(mean && invstd && gamma && beta && mod && off && dgamma && dbeta && dmod && sums && M >= 0 && B > 0 && C > 0 &&
+                  C % 4 == 0 && C <= 4096 && mod_ld >= 2 * C && dmod_ld >= 2 * C && (M == 0 || (dy && x)),
+                  "lotus_adabn_bwd_stats: bad arguments");
+  LOTUS_CHECK_ARG(workspace && workspace_bytes >= lotus_adanorm_workspace(M, B, C), "lotus_adabn_bwd_stats: workspace too small");
+  AdaBnP p;
+  memset(&p, 0, sizeof(p));
+  p.dy = dy; p.x = x; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.mod = mod; p.off = off;
+  p.part = (float*)workspace; p.M = M; p.C = C; p.B = B; p.ld = mod_ld; p.G = ada_chunks(M, B); p.act = act; p.training = 1;
+  hipStream_t st = (hipStream_t)stream;
+  const int c4 = C / 4, tpr = c4 < 256 ? c4 : 256;
+  LOTUS_LAUNCH(adabn_part_kernel, dim3(p.G, B), dim3(256), (size_t)(256 / tpr) * 2 * C * sizeof(float), st, p);
+  LOTUS_LAUNCH(ada_param_reduce_kernel<true>, dim3(cdiv(C, 64)), dim3(256), 0, st, p.part, gamma, beta, mod, mod_ld, dmod, dmod_ld,
+               dgamma, dbeta, B, p.G, C, sums, M);
+  LOTUS_LAUNCH_CHECK("lotus_adabn_bwd_stats");
+  return LOTUS_OK;
+}
+
+// Backward, second half: dx from the all-reduced message (sum dxhat, sum dxhat xhat, rows of all ranks).
+int lotus_adabn_bwd_apply_sums(const float* dy, const float* x, const float* mean, const float* invstd, const float* gamma,
+                               const float* beta, const float* mod, int mod_ld, const int* off, int B, const double* sums, float* dx,
+                               int M, int C, int act, void* stream) {
+  LOTUS_CHECK_ARG(mean && invstd && gamma && beta && mod && off && sums && M >= 0 && B > 0 && C > 0 && C % 4 == 0 && mod_ld >= 2 * C &&
+                  (M == 0 || (dy && x && dx)), "lotus_adabn_bwd_apply_sums: bad arguments");
+  if (M == 0) return LOTUS_OK;
+  AdaBnP p;
+  memset(&p, 0, sizeof(p));
+  p.dy = dy; p.x = x; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.mod = mod; p.off = off; p.y = dx;
+  p.M = M; p.C = C; p.B = B; p.ld = mod_ld; p.act = act; p.training = 1; p.sums = sums;
+  LOTUS_LAUNCH(adabn_cols_kernel, dim3(ada_cols_grid((long)M * C / 4, C)), dim3(256), 0, (hipStream_t)stream, p);
+  LOTUS_LAUNCH_CHECK("lotus_adabn_bwd_apply_sums");
   return LOTUS_OK;
 }
 

@@ -292,7 +292,7 @@ class SimplePolicyPTV3AdaNorm(SimplePolicyPTV3CA):
     (adanorm.PointTransformerV3AdaNorm) — one context vector per cloud — instead of cross attention.  Head, losses, decode,
     forward contract and `last_pred` are SimplePolicyPTV3CA's; the state_dict has the reference's layout (PDNorm sites
     `<site>.norm.*` + `<site>.modulation.1.*`, `txt_attn_fc` only for txt_reduce == 'attn', no CABlocks).
-    fp32 activation storage, one process."""
+    fp32 activation storage; data parallel through parallel.GradReducer + SyncBatchNorm statistics like SimplePolicyPTV3CA."""
 
     def __init__(self, config):
         from .adanorm import PointTransformerV3AdaNorm

@@ -1,9 +1,16 @@
 """SimplePolicyPTV3AdaNorm (v1) against SimplePolicyPTV3CA (v1) at 16 x 4096: forward + loss + backward, samples/s.
 
     python tools/adanorm_bench.py [--steps 20] [--windows 5] [--out path.json]
+    python tools/adanorm_bench.py --rehearsal [--steps 20] [--windows 5] [--out path.json]
 
 The two models alternate window by window in one process (same batch, same warm-up); each reports the median of its
 windows.  The AdaNorm batch carries one instruction token per cloud (txt_reduce 'mean', instr_embed_type 'last').
+
+--rehearsal: the one-rank RCCL rehearsal of the data-parallel AdaNorm step (LOTUS_FORCE_COLLECTIVES=1, nccl backend: every
+collective of the step goes through the real library on one device) against the plain AdaNorm step, alternating windows in one
+process on the training stream.  The rehearsal step is parallel.GradReducer + parallel.enable_sync_batchnorm — bucketed AVG
+all-reduces from backward hooks, the split BatchNorm passes with their fp64 statistics messages — and reports both medians,
+their ratio and the statistics messages per step (9 forward + 9 backward for the five-stage v1 model).
 """
 import argparse
 import json
@@ -34,7 +41,10 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--rehearsal", action="store_true", help="one-rank RCCL data-parallel step against the plain AdaNorm step")
     a = ap.parse_args()
+    if a.rehearsal:
+        return rehearsal(a)
     torch.manual_seed(0)
     batch = au.last_token_batch(synth.augment_clouds(synth.synth_batch(16, 4096, seed=0), seed=1))
     models = {"adanorm": SimplePolicyPTV3AdaNorm(lcfg.preset("adanorm_v1")).cuda().train(),
@@ -67,6 +77,79 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
+
+
+def rehearsal(a):
+    import hashlib
+
+    import torch.distributed as dist
+
+    from robot_3dlotus_amd import _capi, ops, parallel
+
+    os.environ["LOTUS_FORCE_COLLECTIVES"] = "1"
+    parallel.init_distributed()
+    torch.cuda.set_stream(parallel.training_stream())
+    torch.manual_seed(0)
+    b = _dev(au.last_token_batch(synth.augment_clouds(synth.synth_batch(16, 4096, seed=0), seed=1)))
+    plain = SimplePolicyPTV3AdaNorm(lcfg.preset("adanorm_v1")).cuda().train()
+    model = SimplePolicyPTV3AdaNorm(lcfg.preset("adanorm_v1")).cuda().train()
+    model.load_state_dict(plain.state_dict())
+    reducer = parallel.GradReducer(model, bucket_mb=32.0)
+    parallel.enable_sync_batchnorm()
+    hook = ops.BnState.reduce
+    assert hook is not None, "the statistics hook was not installed (no process group?)"
+    params = list(plain.parameters())
+
+    def step_plain():
+        ops.BnState.reduce = None
+        for p in params:
+            p.grad = None
+        _, losses = plain(b, compute_loss=True, compute_final_action=False)
+        losses["total"].backward()
+
+    def step_dp():
+        ops.BnState.reduce = hook
+        reducer.zero_grad()
+        _, losses = model(b, compute_loss=True, compute_final_action=False)
+        losses["total"].backward()
+        reducer.finish()
+
+    steps = {"plain": step_plain, "rehearsal": step_dp}
+    for f in steps.values():
+        for _ in range(a.warmup):
+            f()
+    torch.cuda.synchronize()
+    rates = {k: [] for k in steps}
+    msgs = 0
+    for _ in range(a.windows):
+        for k, f in steps.items():
+            torch.cuda.synchronize()
+            m0 = parallel.BN_MESSAGES
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                f()
+            torch.cuda.synchronize()
+            rates[k].append(16 * a.steps / (time.perf_counter() - t0))
+            if k == "rehearsal":
+                msgs = (parallel.BN_MESSAGES - m0) / a.steps
+            else:
+                assert parallel.BN_MESSAGES == m0, "the plain step sent statistics messages"
+    res = {k: float(np.median(v)) for k, v in rates.items()}
+    res["windows"] = rates
+    res["rehearsal_over_plain"] = res["rehearsal"] / res["plain"]
+    res["bn_messages_per_step"] = msgs
+    res["dist_backend"] = dist.get_backend()
+    res["native_rccl_lanes"] = {"comm": reducer._lane_comm is not None, "main": reducer._lane_main is not None,
+                                "streams_independent": reducer.lanes_independent}
+    res["inplace_fraction"] = reducer.inplace_floats / max(1, reducer.inplace_floats + reducer.copied_floats)
+    res["library_sha256_16"] = hashlib.sha256(open(_capi.LIB_PATH, "rb").read()).hexdigest()[:16]
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    ops.BnState.reduce = None
+    torch.cuda.synchronize()
+    dist.destroy_process_group()
 
 
 if __name__ == "__main__":
