@@ -34,6 +34,7 @@
  *     elementwise entry points is quantised to t / 65536, t >= 1, and kept elements are scaled by 1 / (1 - t / 65536) — the
  *     probability actually applied (round 6); the attention entry points use one hash per element and 1 / (1 - p).
  *   - lotus_abi_version() changes whenever an existing entry point changes its arguments (3 since round 6: lotus_adamw_step took the usage mask; 2 in round 5); bindings check it.
+ *     Entry points ADDED since (adaptive PDNorm, the regression action head: the last two sections) leave it at 3.
  */
 #ifndef LOTUS_HIP_H
 #define LOTUS_HIP_H
@@ -580,6 +581,37 @@ int lotus_adabn_bwd_apply_sums(const float* dy, const float* x, const float* mea
                                int M, int C, int act, void* stream);
 /* PDNorm.modulation[0] = nn.SiLU (model.py:276-278): y = SiLU(x), or y = dy SiLU'(x) when dy is given */
 int lotus_ada_silu(const float* x, const float* dy, float* y, int n, void* stream);
+
+/* ---- regression action head (pos_pred_type 'heatmap_mlp', rot_pred_type 'euler' / 'quat'; fp32 activations only, no bf16
+ * twin) ---------------------------------------------------------------------------------------------------------------- */
+/* ActionHead.forward, heatmap_mlp branch, simple_policy_ptv3.py:46-53,83-103: e = h w3^T + b3 ([n][4], kept for backward; h [n][C]
+ * is the hidden layer after LeakyReLU and dropout, w3 [4][C], C % 4 == 0), and per cloud b (rows off[b] .. off[b + 1], any size
+ * >= 1):  xt[b] = sum_i softmax_i(e_i0 / temp) (pc_i[0:3] + e_i[1:4])  with pc = point rows whose first three columns are xyz (row
+ * stride ld).  stats [B][2] (double) = (max, log-sum-exp) of e_i0 / temp.  The maximum is subtracted before every exponential and the
+ * sums are carried in double over a (cloud, row chunk) grid merged in fixed order: no atomics, bit-reproducible. */
+size_t lotus_softpos_workspace(int B);
+int lotus_softpos_fwd(const float* h, const float* w3, const float* b3, const float* pc, long ld, const int* off, int B, int n,
+                      int C, double temp, float* e, float* xt, double* stats, void* workspace, size_t workspace_bytes,
+                      void* stream);
+/* de [n][4] from g [B][3] = dL / dxt: with p_i = exp(e_i0 / temp - lse_b), q_i = pc_i[0:3] + e_i[1:4]:
+ * de_i[1:4] = p_i g_b, de_i0 = p_i ((q_i - xt_b) . g_b) / temp (autograd of simple_policy_ptv3.py:89-103).  batch [n] = cloud of row i. */
+int lotus_softpos_bwd(const float* g, const float* e, const float* pc, long ld, const int* batch, const double* stats,
+                      const float* xt, int B, int n, double temp, float* de, void* stream);
+/* compute_loss on the [B]-sized tensors, simple_policy_ptv3.py:142-152 (rotation slice, quaternion normalisation) and :322-368,
+ * one launch.  ae [B][W]: rotation in the leading columns, openness logit in the LAST column; gt [B][ga] (ga = 7, 8 for quat):
+ * position 0..2, rotation 3..ga-2, openness ga-1.  rot_kind 0 = euler_disc (W = nrot*3 + 1, cross entropy as lotus_loss_fwd),
+ * 1 = euler (columns 0..2; per element the smaller of the squared errors against the target and the target -+ 2, :349-357),
+ * 2 = quat (columns 0..3 normalised without epsilon into xr [B][4]; per row the smaller of the mean squared errors against the
+ * target and its negative, :337-343; the gradient passes through the normalisation).  The selections are constants in backward.
+ * Position: xt [B][3] (heatmap_mlp: MSE, :334) or ce (heatmap_disc: ce[(b*3 + c) * ce_ld] = cross entropy of cloud b, axis c from
+ * lotus_pos_ce_fwd) -- exactly one of them.  losses[4] = pos, rot, open, total (= pos_w pos + rot_w rot + open).  dae [B][W] and
+ * dpos [B][3] keep the partial derivatives (d pos / d xt, or d pos / d ce) for lotus_reg_loss_bwd, which scales them by the
+ * upstream gradient gl[4] (device); columns of ae that enter no loss get an exact 0.  gt == null: only xr is written. */
+int lotus_reg_loss_fwd(const float* ae, const float* gt, const float* xt, const float* ce, int ce_ld, int B, int W, int ga,
+                       int rot_kind, int nrot, float pos_w, float rot_w, float* losses, float* dae, float* dpos, float* xr,
+                       void* stream);
+int lotus_reg_loss_bwd(const float* dae, const float* dpos, const float* gl, float pos_w, float rot_w, int B, int W, float* dae_out,
+                       float* dpos_out, void* stream);
 
 #ifdef __cplusplus
 }

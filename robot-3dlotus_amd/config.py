@@ -167,10 +167,18 @@ ADANORM_OVERRIDES = {"adanorm_v1": V1_OVERRIDES + ADANORM_SWITCHES, "adanorm_tin
                      "adanorm_tinyctx": TINYCTX_OVERRIDES + ADANORM_SWITCHES}
 
 
+# The regression head of the YAML's own defaults (simple_policy_ptv3.yaml: pos_pred_type 'heatmap_mlp', rot_pred_type 'euler')
+# on the published networks; dim_actions stays 7 (3 angles + openness from action_mlp)
+REG_SWITCHES = ["action_config.pos_pred_type", "heatmap_mlp", "action_config.rot_pred_type", "euler"]
+REG_OVERRIDES = {"tiny_reg": TINY_OVERRIDES + REG_SWITCHES, "v1_reg": V1_OVERRIDES + REG_SWITCHES,
+                 "adanorm_tiny_reg": ADANORM_OVERRIDES["adanorm_tiny"] + REG_SWITCHES}
+
+
 def preset(name="v1"):
     """'v1' / 'tiny': 3D-LOTUS policy; 'peract': the RLBench-18task (PerAct) variant of BASELINE configs[4] (same network;
     its bf16 compute mode is ops.set_gemm_precision("bf16")); 'mp' / 'mp_tiny': 3D-LOTUS++ motion planner (configs[3]);
-    'adanorm_v1' / 'adanorm_tiny' / 'adanorm_tinyctx': the policy networks as SimplePolicyPTV3AdaNorm (adaptive PDNorm)."""
+    'adanorm_v1' / 'adanorm_tiny' / 'adanorm_tinyctx': the policy networks as SimplePolicyPTV3AdaNorm (adaptive PDNorm);
+    'tiny_reg' / 'v1_reg' / 'adanorm_tiny_reg': their base preset with the regression head (heatmap_mlp positions, euler)."""
     if name in ("mp", "mp_tiny", "mp_tinyctx"):
         model = copy.deepcopy(_YAML_MODEL)
         model["model_class"] = _YAML_MP_DELTA["model_class"]
@@ -178,6 +186,8 @@ def preset(name="v1"):
         return to_cfg(merge_overrides(model, {"mp": MP_OVERRIDES, "mp_tiny": MP_TINY_OVERRIDES, "mp_tinyctx": MP_TINYCTX_OVERRIDES}[name]))
     if name in ADANORM_OVERRIDES:
         return load_model_config(None, ADANORM_OVERRIDES[name])
+    if name in REG_OVERRIDES:
+        return load_model_config(None, REG_OVERRIDES[name])
     return load_model_config(None, {"v1": V1_OVERRIDES, "tiny": TINY_OVERRIDES, "peract": PERACT_OVERRIDES,
                                     "tinydeep": TINYDEEP_OVERRIDES, "tinyctx": TINYCTX_OVERRIDES}[name])
 

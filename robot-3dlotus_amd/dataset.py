@@ -198,7 +198,7 @@ def soft_position_labels(xyz, gt_pos, pos_bins, pos_bin_size, kind="plain", robo
 # --------------------------------------------------------------------------------------------- dataset
 class KeystepDataset(torch.utils.data.Dataset):
     """Items of the reference's `SimplePolicyDataset` (constructor arguments of the same names and meaning) for
-    rot_type 'euler_disc'.  One item = one episode (all key steps but the last) when `all_step_in_batch`, else one step."""
+    rot_type 'euler_disc', 'euler' (xyz Euler angles / 180, in [-1, 1]) and 'quat' (xyzw, gt_actions [8]).  One item = one episode (all key steps but the last) when `all_step_in_batch`, else one step."""
 
     def __init__(self, data_dir, instr_embed_file, taskvar_instr_file, taskvar_file=None, num_points=10000,
                  xyz_shift="center", xyz_norm=True, use_height=False, rot_type="euler_disc", instr_embed_type="last",
@@ -206,9 +206,12 @@ class KeystepDataset(torch.utils.data.Dataset):
                  sample_points_by_distance=False, same_npoints_per_example=False, rm_pc_outliers=False,
                  euler_resolution=5, pos_type="disc", pos_bins=50, pos_bin_size=0.01, pos_heatmap_type="plain",
                  pos_heatmap_no_robot=False, aug_max_rot=45, real_robot=False, host_labels=False, store=None, **_unused):
-        if rot_type != "euler_disc" or real_robot or rm_pc_outliers:
-            raise NotImplementedError("lotus-hip reads the published configuration family: rot_type euler_disc, simulated "
-                                      "robot, no outlier filter")
+        if rot_type not in ("euler_disc", "euler", "quat"):
+            raise NotImplementedError(f"rot_type={rot_type!r}: lotus-hip builds the rotation targets 'euler_disc', 'euler' and 'quat'")
+        if real_robot or rm_pc_outliers:
+            raise NotImplementedError("lotus-hip reads the published configuration family: simulated robot, no outlier filter")
+        if pos_type not in ("disc", "cont"):
+            raise ValueError(f"pos_type={pos_type!r}")
         if xyz_shift not in ("none", "center", "gripper") or rm_robot not in ("none", "box", "box_keep_gripper"):
             raise ValueError(f"xyz_shift={xyz_shift!r} / rm_robot={rm_robot!r}")
         self.taskvar_instrs = json.load(open(taskvar_instr_file))
@@ -232,7 +235,7 @@ class KeystepDataset(torch.utils.data.Dataset):
                         by_distance=sample_points_by_distance, same_npoints=same_npoints_per_example,
                         euler_resolution=euler_resolution, pos_type=pos_type, pos_bins=pos_bins, pos_bin_size=pos_bin_size,
                         heatmap=pos_heatmap_type, no_robot=pos_heatmap_no_robot, max_rot=np.deg2rad(aug_max_rot),
-                        host_labels=host_labels)
+                        host_labels=host_labels, rot_type=rot_type)
 
     def __len__(self):
         return len(self.ids)
@@ -251,8 +254,17 @@ class KeystepDataset(torch.utils.data.Dataset):
         keep = int(n * np.random.uniform(0.95, 1))
         return np.random.permutation(n)[:keep]
 
+    def _rot_target(self, quat):
+        """Rotation target of one orientation (xyzw) in the configured rot_type (simple_policy_dataset.py:166-172,183-203)."""
+        kind = self.opt["rot_type"]
+        if kind == "quat":
+            return np.asarray(quat)
+        if kind == "euler":
+            return Rotation.from_quat(quat).as_euler("xyz", degrees=True) / 180.0
+        return quaternion_to_discrete_euler(quat, self.opt["euler_resolution"])
+
     def _augment(self, xyz, ee_pose, gt_action):
-        """z rotation of the scene (cloud, both poses, both orientations) + U(0, 2 mm) jitter (:158-181); the discrete
+        """z rotation of the scene (cloud, both poses, both orientations) + U(0, 2 mm) jitter (:158-181); the
         rotation target is recomputed from the rotated target orientation."""
         angle = np.random.uniform(-1, 1) * self.opt["max_rot"]
         turn = Rotation.from_euler("z", angle)
@@ -261,7 +273,7 @@ class KeystepDataset(torch.utils.data.Dataset):
             pose[:3] = rotate_z(pose[:3], angle)
         for pose in (ee_pose, gt_action):
             pose[3:7] = (turn * Rotation.from_quat(pose[3:7])).as_quat()
-        rot = quaternion_to_discrete_euler(gt_action[3:7], self.opt["euler_resolution"])
+        rot = self._rot_target(gt_action[3:7])
         return xyz + np.random.uniform(0, 0.002, size=xyz.shape), rot
 
     def __getitem__(self, idx):
@@ -271,8 +283,12 @@ class KeystepDataset(torch.utils.data.Dataset):
         actions = np.asarray(ep["action"])
         T = len(ep["xyz"])
         # rotation target of step t = orientation of the NEXT key pose (the last one repeats) (:188-190)
-        nxt = [quaternion_to_discrete_euler(q, o["euler_resolution"]) for q in actions[1:, 3:7]]
-        rot_targets = np.stack(nxt + nxt[-1:])
+        if o["rot_type"] == "quat":
+            # (:200-201: the step's OWN orientation followed by a repeat of the last one — no shift to the next key pose)
+            rot_targets = np.concatenate([actions[:, 3:7], actions[-1:, 3:7]], 0)
+        else:
+            nxt = [self._rot_target(q) for q in actions[1:, 3:7]]
+            rot_targets = np.stack(nxt + nxt[-1:])
         out = {k: [] for k in ("data_ids", "pc_fts", "step_ids", "pc_centroids", "pc_radius", "ee_poses", "txt_embeds", "gt_actions")}
         if o["pos_type"] == "disc" and o["host_labels"]:
             out["disc_pos_probs"] = []

@@ -9,6 +9,8 @@ backward that chains the HIP kernels (fused epilogues, no temporaries beyond wha
   CrossAttnFn  x + proj(cross_attention(q(LN(x)), kv(context)))    CABlock.attn model_ca.py:135-140
   StemFn / PoolFn / UnpoolFn / HeadLossFn                          Embedding, SerializedPooling,
                                                                    SerializedUnpooling, ActionHead+loss
+  RegHeadLossFn                                                    ActionHead+loss with heatmap_mlp positions and / or
+                                                                   euler / quat rotations (csrc/reg_head.hip)
 PyTorch provides device memory, the stream and the autograd graph; all arithmetic is in the kernels.
 """
 import os
@@ -1844,6 +1846,117 @@ class HeadLossFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         call("lotus_cloud_max_bwd", dpc, arg, lvl.batch, N, C, dxh, dx)
         return (dx, dhw0, dhb0, dhw3, dhb3, daw0, dab0, daw3, dab3) + (None,) * 8
+
+
+ROT_KINDS = {"euler_disc": 0, "euler": 1, "quat": 2}  # rot_kind of lotus_reg_loss_fwd
+
+
+def softpos_fwd(h, w3, b3, pc_fts, lvl, temp):
+    """e = h w3^T + b3 [N, 4] and the per-cloud soft position xt [B, 3] = sum_i softmax_i(e_i0 / temp) (xyz_i + e_i[1:4])
+    (simple_policy_ptv3.py:83-103); pc_fts [N, >= 3] fp32 with unit column stride.  -> (e, xt, stats [B, 2] f64 = max, lse)."""
+    N, C = h.shape
+    B = len(lvl.counts)
+    assert pc_fts.dtype == torch.float32 and pc_fts.stride(1) == 1 and pc_fts.shape[0] == N and w3.shape == (4, C)
+    e = torch.empty(N, 4, dtype=torch.float32, device=h.device)
+    xt = torch.empty(B, 3, dtype=torch.float32, device=h.device)
+    stats = torch.empty(B, 2, dtype=torch.float64, device=h.device)
+    ws = _ws(query("lotus_softpos_workspace", B), h.device)
+    call("lotus_softpos_fwd", h, w3, b3, pc_fts, pc_fts.stride(0), lvl.off, B, N, C, float(temp), e, xt, stats, ws, ws.numel())
+    return e, xt, stats
+
+
+def softpos_bwd(g, e, pc_fts, lvl, stats, xt, temp):
+    """de [N, 4] of softpos_fwd from g [B, 3] = dL / dxt."""
+    de = torch.empty_like(e)
+    call("lotus_softpos_bwd", g, e, pc_fts, pc_fts.stride(0), lvl.batch, stats, xt, len(lvl.counts), e.shape[0], float(temp), de)
+    return de
+
+
+class RegHeadLossFn(torch.autograd.Function):
+    """ActionHead with a regression option (pos_pred_type 'heatmap_mlp' and / or rot_pred_type 'euler' / 'quat') +
+    compute_loss, simple_policy_ptv3.py:46-53,83-103,113-157,:308-373.  fp32 activation storage.  Returns (losses[4] = pos,
+    rot, open, total; xt = the soft position [B, 3] ('heatmap_mlp') or the heat-map logits [N, 3*2*pos_bins];
+    the rotation = ae for 'euler_disc', ae[:, :3] for 'euler', the normalised quaternion [B, 4]; xo = ae[:, -1]).
+    pc_fts [N, >= 3] holds the coordinates (row stride = its width); temp = pos_heatmap_temp."""
+
+    @_fwd
+    def forward(ctx, x, hw0, hb0, hw3, hb3, aw0, ab0, aw3, ab3, lvl, tgt, gt, pc_fts, pos_type, rot_type, temp, pos_w, rot_w,
+                drop_p, seed, with_loss):
+        assert not _capi.BF16, "the regression head runs with fp32 activation storage"
+        dev = x.device
+        N, C = x.shape
+        B = len(lvl.counts)
+        mlp, kind = pos_type == "heatmap_mlp", ROT_KINDS[rot_type]
+        h, hpre = linear_fwd(x, hw0, hb0, act=ACT_LEAKY, save_pre=True, drop_p=drop_p, seed=seed)
+        if ARG_TAP is not None or ARG_INJECT:
+            hpre = _arg_hook("leaky", hpre)
+        e = stats = None
+        if mlp:
+            e, xt, stats = softpos_fwd(h, hw3, hb3, pc_fts, lvl, temp)
+        else:
+            xt, _ = linear_fwd(h, hw3, hb3)
+        pc = torch.empty(B, C, dtype=x.dtype, device=dev)
+        arg = torch.empty(B, C, dtype=torch.int32, device=dev)
+        ws = _ws(query("lotus_cloud_max_workspace", B, C), x.device)
+        call("lotus_cloud_max_fwd", x, lvl.off, B, C, pc, arg, ws, ws.numel())
+        if ARG_TAP is not None or ARG_INJECT:
+            arg = _arg_hook("cloud", arg)
+        a, apre = linear_fwd(pc, aw0, ab0, act=ACT_LEAKY, save_pre=True, drop_p=drop_p, seed=mix_seed(seed, 1))
+        ae, _ = linear_fwd(a, aw3, ab3)
+        W = ae.shape[1]
+        nb = 0 if mlp else xt.shape[1] // 3
+        nrot = (W - 1) // 3 if kind == 0 else 0
+        losses = torch.zeros(4, dtype=torch.float32, device=dev)
+        dae = torch.empty(B, W, dtype=torch.float32, device=dev)
+        dpos = torch.empty(B, 3, dtype=torch.float32, device=dev)
+        xr = torch.empty(B, 4, dtype=torch.float32, device=dev) if kind == 2 else None
+        ce = None
+        if with_loss and not mlp:
+            ce = torch.empty(query("lotus_loss_stats_floats", B), dtype=torch.float32, device=dev)
+            call("lotus_pos_ce_fwd", xt, tgt, lvl.off, B, nb, ce)
+        if with_loss or kind == 2:
+            call("lotus_reg_loss_fwd", ae, gt if with_loss else None, xt if (with_loss and mlp) else None, ce, 4, B, W,
+                 gt.shape[1] if with_loss else 0, kind, nrot, float(pos_w), float(rot_w), losses, dae, dpos, xr)
+        empty = x.new_empty(0)
+        ctx.save_for_backward(x, hw0, hw3, aw0, aw3, h, hpre, xt, pc, arg, a, apre, dae, dpos, pc_fts,
+                              e if mlp else empty, stats if mlp else empty, ce if ce is not None else empty,
+                              tgt if not mlp else empty)
+        ctx.meta = (lvl, pos_w, rot_w, drop_p, seed, with_loss, mlp, nb, float(temp))
+        rot = xr if kind == 2 else (ae[:, :3] if kind == 1 else ae)
+        xo = ae[:, -1]
+        ctx.mark_non_differentiable(xt, rot, xo)
+        return losses, xt, rot, xo
+
+    @_joined
+    def backward(ctx, gl, _gxt, _grot, _gxo):
+        x, hw0, hw3, aw0, aw3, h, hpre, xt, pc, arg, a, apre, dae, dpos, pc_fts, e, stats, ce, tgt = ctx.saved_tensors
+        lvl, pos_w, rot_w, p, seed, with_loss, mlp, nb, temp = ctx.meta
+        assert with_loss, "backward through the head requires compute_loss=True"
+        dev = x.device
+        N, C = x.shape
+        B, W = dae.shape
+        gl = gl.contiguous()
+        dae_o = torch.empty_like(dae)
+        gpos = torch.empty_like(dpos)
+        call("lotus_reg_loss_bwd", dae, dpos, gl, float(pos_w), float(rot_w), B, W, dae_o, gpos)
+        # action branch (B rows)
+        daw3, dab3 = linear_wgrad(dae_o, a)
+        dapre = linear_dgrad(dae_o, aw3, pre=apre, act=ACT_LEAKY, drop_p=p, seed=mix_seed(seed, 1))
+        daw0, dab0 = linear_wgrad(dapre, pc)
+        dpc = linear_dgrad(dapre, aw0)
+        # heatmap branch (N rows): d e [N, 4] of the soft position, or d xt of the heat-map cross entropy
+        if mlp:
+            dxt = softpos_bwd(gpos, e, pc_fts, lvl, stats, xt, temp)
+        else:
+            dxt = torch.empty_like(xt)
+            call("lotus_pos_ce_bwd", xt, tgt, lvl.off, lvl.batch, ce, gpos, B, N, nb, dxt)
+        dhw3, dhb3 = linear_wgrad(dxt, h)
+        dhpre = linear_dgrad(dxt, hw3, pre=hpre, act=ACT_LEAKY, drop_p=p, seed=seed)
+        dhw0, dhb0 = linear_wgrad(dhpre, x)
+        dxh = linear_dgrad(dhpre, hw0)
+        dx = torch.empty_like(x)
+        call("lotus_cloud_max_bwd", dpc, arg, lvl.batch, N, C, dxh, dx)
+        return (dx, dhw0, dhb0, dhw3, dhb3, daw0, dab0, daw3, dab3) + (None,) * 12
 
 
 class StepHeadFn(torch.autograd.Function):

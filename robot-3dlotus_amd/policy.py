@@ -73,20 +73,42 @@ class BaseModel(nn.Module):
             nn.init.trunc_normal_(m.weight, std=0.02)
 
 
+_POS_REFUSED = ("heatmap_mlp3", "heatmap_mlp_topk", "heatmap_mlp_clf", "heatmap_normmax")
+_ROT_REFUSED = ("rot6d", "euler_delta")
+
+
 class ActionHead(nn.Module):
-    """Parameter layout of simple_policy_ptv3.py:19-68 for (max, heatmap_disc, euler_disc)."""
+    """Parameter layout of simple_policy_ptv3.py:19-68 for reduce = max, pos_pred_type heatmap_disc | heatmap_mlp and
+    rot_pred_type euler_disc | euler | quat (the other options of the reference are refused by name)."""
 
     def __init__(self, reduce, pos_pred_type, rot_pred_type, hidden_size, dim_actions, dropout=0, voxel_size=0.01,
                  euler_resolution=5, ptv3_config=None, pos_bins=50):
         super().__init__()
-        if (reduce, pos_pred_type, rot_pred_type) != ("max", "heatmap_disc", "euler_disc"):
-            raise NotImplementedError("lotus-hip builds the published head: reduce=max, heatmap_disc, euler_disc")
+        if reduce != "max":
+            raise NotImplementedError(f"reduce={reduce!r}: lotus-hip builds the action head with reduce='max' only")
+        if pos_pred_type not in ("heatmap_disc", "heatmap_mlp"):
+            why = " (unfinished in the reference)" if pos_pred_type in _POS_REFUSED else ""
+            raise NotImplementedError(f"pos_pred_type={pos_pred_type!r}{why}: lotus-hip builds 'heatmap_disc' and 'heatmap_mlp'")
+        if rot_pred_type not in ("euler_disc", "euler", "quat"):
+            why = " (not built)" if rot_pred_type in _ROT_REFUSED else ""
+            raise NotImplementedError(f"rot_pred_type={rot_pred_type!r}{why}: lotus-hip builds 'euler_disc', 'euler' and 'quat'")
+        need = {"euler_disc": 7, "euler": 7, "quat": 8}[rot_pred_type]
+        if rot_pred_type != "euler_disc" and dim_actions < need:
+            # action_mlp has dim_actions - 3 outputs and the LAST one is the openness logit (simple_policy_ptv3.py:58,142-152)
+            raise ValueError(f"rot_pred_type={rot_pred_type!r} needs dim_actions >= {need}, got dim_actions={dim_actions}")
+        self.reduce, self.pos_pred_type, self.rot_pred_type = reduce, pos_pred_type, rot_pred_type
         self.euler_resolution, self.euler_bins, self.pos_bins = euler_resolution, 360 // euler_resolution, pos_bins
         self.dropout = float(dropout)
         self.heatmap_mlp = nn.Sequential(nn.Linear(hidden_size, hidden_size), nn.LeakyReLU(0.02), nn.Dropout(dropout),
-                                         nn.Linear(hidden_size, 3 * pos_bins * 2))
+                                         nn.Linear(hidden_size, 3 * pos_bins * 2 if pos_pred_type == "heatmap_disc" else 4))
         self.action_mlp = nn.Sequential(nn.Linear(hidden_size, hidden_size), nn.LeakyReLU(0.02), nn.Dropout(dropout),
-                                        nn.Linear(hidden_size, self.euler_bins * 3 + 1))
+                                        nn.Linear(hidden_size, self.euler_bins * 3 + 1 if rot_pred_type == "euler_disc"
+                                                  else dim_actions - 3))
+
+    @property
+    def published(self):
+        """the head of the published job scripts (heatmap_disc, euler_disc): ops.HeadLossFn; everything else ops.RegHeadLossFn"""
+        return self.pos_pred_type == "heatmap_disc" and self.rot_pred_type == "euler_disc"
 
 
 class RobotPoseEmbedding(nn.Module):
@@ -203,6 +225,10 @@ class SimplePolicyPTV3CA(BaseModel):
 
     def forward(self, batch, compute_loss=False, **kwargs):
         if self.act_storage == "bf16":
+            head = self.act_proj_head
+            if not head.published:
+                raise NotImplementedError(f"act_storage='bf16' is not built for pos_pred_type={head.pos_pred_type!r} with "
+                                          f"rot_pred_type={head.rot_pred_type!r} (fp32 activations only)")
             if self.weight_shadows:
                 self._shadows()
             with ops.storage(torch.bfloat16, shadows=self.weight_shadows):
@@ -223,6 +249,8 @@ class SimplePolicyPTV3CA(BaseModel):
         if dev.type != "cuda":
             raise RuntimeError("lotus-hip runs on a HIP device only (no CPU fallback); move the model and batch to cuda")
         act, head = self.config.action_config, self.act_proj_head
+        if not head.published:
+            return self._forward_reg(batch, compute_loss, **kwargs)
         outs = self.ptv3_model(self.prepare_ptv3_batch(batch), return_dec_layers=True)
         last = outs[-1]
         lvl = last.level
@@ -285,6 +313,80 @@ class SimplePolicyPTV3CA(BaseModel):
             return final, {"pos": losses[0], "rot": losses[1], "open": losses[2], "total": losses[3]}
         return final
 
+    def _forward_reg(self, batch, compute_loss=False, **kwargs):
+        """The head with a regression option (pos_pred_type 'heatmap_mlp' and / or rot_pred_type 'euler' / 'quat'),
+        simple_policy_ptv3.py:238-306: ops.RegHeadLossFn, then the reference's decode.  `batch` is prepared already."""
+        dev = batch["pc_fts"].device
+        act, head = self.config.action_config, self.act_proj_head
+        mlp = head.pos_pred_type == "heatmap_mlp"
+        outs = self.ptv3_model(self.prepare_ptv3_batch(batch), return_dec_layers=True)
+        last = outs[-1]
+        lvl = last.level
+        B = len(lvl.counts)
+        gt = batch["gt_actions"].float().contiguous() if "gt_actions" in batch else None
+        with_loss = bool(compute_loss)
+        ga = 8 if head.rot_pred_type == "quat" else 7
+        if with_loss and (gt is None or gt.shape[-1] != ga):
+            raise ValueError(f"rot_pred_type={head.rot_pred_type!r} takes gt_actions [B, {ga}], got "
+                             f"{None if gt is None else tuple(gt.shape)}")
+        pc = batch["pc_fts"] if batch["pc_fts"].stride(1) == 1 else batch["pc_fts"].contiguous()
+        pc = pc.float()
+        tgt = None
+        if with_loss and not mlp:
+            dp = batch.get("disc_pos_probs")
+            if dp is None:
+                tgt = ops.pos_targets(pc, lvl.off, lvl.batch, gt, 2 * head.pos_bins, act.pos_bin_size,
+                                      batch.get("pos_heatmap_type", "plain"), batch.get("robot_point_mask"))
+            else:
+                tgt = dp if isinstance(dp, torch.Tensor) else torch.cat([t.reshape(-1) for t in dp]).to(dev)
+                tgt = tgt.float().contiguous()
+        hm, am = head.heatmap_mlp, head.action_mlp
+        p = head.dropout if self.training else 0.0
+        lc = self.config.loss_config
+        dummy = last.feat.new_zeros(1)
+        losses, xt, rot, pred_open = ops.RegHeadLossFn.apply(
+            last.feat, hm[0].weight, hm[0].bias, hm[3].weight, hm[3].bias, am[0].weight, am[0].bias, am[3].weight,
+            am[3].bias, lvl, tgt if tgt is not None else dummy, gt if with_loss else dummy.view(1, 1), pc,
+            head.pos_pred_type, head.rot_pred_type, float(act.get("pos_heatmap_temp", 1)), float(lc.pos_weight),
+            float(lc.rot_weight), p, ops.mix_seed(self.ptv3_model.last_seed, 1000), with_loss)
+        nb = 2 * head.pos_bins
+        pred_pos = xt if mlp else xt.view(-1, 3, nb).permute(1, 0, 2)
+        pred_rot = rot[:, :head.euler_bins * 3].view(B, head.euler_bins, 3) if head.rot_pred_type == "euler_disc" else rot
+        self.last_pred = (pred_pos, pred_rot, pred_open)
+        loss_dict = {"pos": losses[0], "rot": losses[1], "open": losses[2], "total": losses[3]}
+
+        decode = kwargs.get("compute_final_action", True)
+        if compute_loss and self.training and not decode and not kwargs.get("decode_actions", False):
+            return None, loss_dict      # the training step: the action tuple is discarded (see _forward)
+        if mlp:
+            pos = xt                    # compute_final_action has no effect on a continuous position
+        elif decode:
+            best = act.get("best_disc_pos", "max")
+            if best == "ens1":
+                pos = ops.pos_decode_ens1(xt, pc, list(batch["npoints_in_batch"]), nb, act.pos_bin_size)
+            elif best == "max":
+                pos = ops.pos_decode_max(xt, pc, lvl.off, B, nb, act.pos_bin_size)
+            else:
+                raise ValueError(f"best_disc_pos must be 'max' or 'ens1', got {best!r}")
+            pos = pos.float()           # (simple_policy_ptv3.py:273)
+        else:
+            pos = gt[..., :3]
+        from scipy.spatial.transform import Rotation as R
+        if head.rot_pred_type == "euler_disc":
+            # float64 quaternions: torch.cat promotes the whole action (simple_policy_ptv3.py:292-296)
+            rot_bins = torch.argmax(pred_rot, 1).cpu().numpy()
+            quat = np.stack([R.from_euler("xyz", x * head.euler_resolution - 180, degrees=True).as_quat() for x in rot_bins], 0)
+            quat = torch.from_numpy(quat).to(dev)
+        elif head.rot_pred_type == "euler":
+            # simple_policy_ptv3.py:284-286 (RotationMatrixTransform.euler_to_quaternion: scipy 'xyz' in degrees), float32
+            eul = (pred_rot.detach() * 180).cpu().numpy()
+            quat = torch.from_numpy(R.from_euler("xyz", eul, degrees=True).as_quat()).float().to(dev)
+        else:
+            quat = pred_rot.detach()
+        final = torch.cat([pos, quat, pred_open.detach().unsqueeze(-1)], -1)
+        if compute_loss:
+            return final, loss_dict
+        return final
 
 
 class SimplePolicyPTV3AdaNorm(SimplePolicyPTV3CA):

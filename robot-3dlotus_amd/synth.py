@@ -51,10 +51,14 @@ def synth_cloud(rng, n):
 
 
 def synth_batch(batch_size=16, npoints=4096, ragged=False, seed=0, pos_bins=15, txt_dim=512,
-                real_soft_labels=False):
+                real_soft_labels=False, rot_type="euler_disc"):
     """Returns a dict with the reference batch schema: pc_fts f32[N,7],
     npoints_in_batch list, offset i64[B], txt_embeds f32[sumL,512], txt_lens list, gt_actions
-    f32[B,7], disc_pos_probs list of f32[3, n*2*pos_bins], ee_poses, step_ids."""
+    f32[B,7], disc_pos_probs list of f32[3, n*2*pos_bins], ee_poses, step_ids.
+    rot_type (simple_policy_dataset.py:166-170,185-187) sets the rotation columns of gt_actions: 'euler_disc' bins 0..71,
+    'euler' angles / 180 in (-1, 1), both [B,7]; 'quat' unit quaternions xyzw, [B,8].  Everything else is the same batch."""
+    if rot_type not in ("euler_disc", "euler", "quat"):
+        raise ValueError(f"synth_batch: rot_type must be 'euler_disc', 'euler' or 'quat', got {rot_type!r}")
     rng = np.random.default_rng(seed)
     pcs, txt, probs = [], [], []
     for b in range(batch_size):
@@ -75,6 +79,16 @@ def synth_batch(batch_size=16, npoints=4096, ragged=False, seed=0, pos_bins=15, 
     quat = rng2.standard_normal((batch_size, 4))
     quat /= np.linalg.norm(quat, axis=1, keepdims=True)
     ee = np.concatenate([rng2.normal(0, 0.3, size=(batch_size, 3)), quat, rng2.integers(0, 2, size=(batch_size, 1))], 1).astype(np.float32)
+    step_ids = rng2.integers(0, 30, size=batch_size)
+    if rot_type != "euler_disc":
+        # continuous rotation labels from a third generator: the two streams above stay as they are
+        rng3 = np.random.default_rng([seed, 0x407])
+        if rot_type == "euler":
+            rot = rng3.uniform(-1.0, 1.0, size=(batch_size, 3))
+        else:
+            rot = rng3.standard_normal((batch_size, 4))
+            rot /= np.linalg.norm(rot, axis=1, keepdims=True)
+        gt = np.concatenate([gt[:, :3], rot.astype(np.float32), gt[:, -1:]], 1)
     return {
         "pc_fts": torch.from_numpy(np.concatenate(pcs, 0)),
         "npoints_in_batch": npts,
@@ -84,7 +98,7 @@ def synth_batch(batch_size=16, npoints=4096, ragged=False, seed=0, pos_bins=15, 
         "gt_actions": torch.from_numpy(gt),
         "disc_pos_probs": [torch.from_numpy(p) for p in probs],
         "ee_poses": torch.from_numpy(ee),
-        "step_ids": torch.from_numpy(rng2.integers(0, 30, size=batch_size)).long(),
+        "step_ids": torch.from_numpy(step_ids).long(),
     }
 
 
