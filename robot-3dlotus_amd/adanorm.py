@@ -5,6 +5,9 @@ PDNorm(adaptive=True, decouple=False) (model.py:257-303): BatchNorm at the stem,
 LayerNorm at `cpe.2`, `norm1` and `norm2` of every Block.  Norm j of width C is modulated by one vector per cloud,
 [shift_j | scale_j] = Linear_j(SiLU(c_b)), c_b the instruction (+ pose, + step) context of cloud b.
 
+PointTransformerV3AdaNorm is ptv3.PointTransformerV3CA's skeleton (constructor, forward prologue, encoder / decoder walk) with the
+PDNorm modules and steps overridden; the Block sub-block nodes run ops.{cpe,selfattn,ffn}_branch_{fwd,bwd} — the bodies they share
+with ops.CpeFn / SelfAttnFn / FfnFn — between adaln_fwd and adaln_bwd.
 The autograd nodes below are composed of the library's existing per-launch primitives (sparse convolution, dense layers,
 patch attention, BatchNorm statistics) and the modulated-norm entry points of csrc/adanorm.hip.  Under data parallel
 (parallel.GradReducer + parallel.enable_sync_batchnorm) the 13 BatchNorm sites of a five-stage model run split — statistics ->
@@ -19,7 +22,6 @@ import torch.nn as nn
 
 from . import ops
 from ._capi import call, query, WS
-from .frontend import FrontEnd, draw_order_perms
 from .ops import ACT_GELU, BN_EPS, BN_MOMENTUM, _fwd, _joined, mix_seed
 from .ptv3 import PointTransformerV3CA, SubMConv3d, _Attn, _MLP, _bn
 
@@ -232,8 +234,7 @@ class AdaCpeFn(torch.autograd.Function):
         same = xs is x
         if wt is None:
             wt = ops.conv_weight_t(cw)
-        c = ops.conv_fwd(xs, cw, cb, lvl.nbr27, lvl.order[0], w_t=wt, tap_plan=lvl.tap_plan)
-        l, _ = ops.linear_fwd(c, lw, lb)
+        c, l = ops.cpe_branch_fwd(xs, cw, cb, lw, lb, lvl, wt)
         y, mean, rstd = adaln_fwd(l, g, b, mod, lvl, res=x)
         ctx.meta = (lvl, same, bank, j)
         ctx.save_for_backward(xs, cw, lw, g, b, mod, c, l, mean, rstd, wt)
@@ -246,14 +247,8 @@ class AdaCpeFn(torch.autograd.Function):
         dy = dy.contiguous()
         dmod = bank.grad_slice(j)
         dl, dg, db = adaln_bwd(dy, l, mean, rstd, g, b, mod, dmod, lvl)
-        dlw, dlb = ops.linear_wgrad(dl, c)
-        dc = ops.linear_dgrad(dl, lw)
-        dcw, dcb = ops.conv_wgrad(dc, xs, cw.shape, lvl.nbr27)
-        if same:
-            dx = ops.conv_dgrad(dc, cw, lvl.nbr27, lvl.order[0], add=dy, w_t=wt, lvl=lvl, tap_plan=lvl.tap_plan)
-            return dx, None, dmod, dcw, dcb, dlw, dlb, dg, db, None, None, None, None
-        dxs = ops.conv_dgrad(dc, cw, lvl.nbr27, lvl.order[0], w_t=wt, lvl=lvl, tap_plan=lvl.tap_plan)
-        return dy, dxs, dmod, dcw, dcb, dlw, dlb, dg, db, None, None, None, None
+        dx, dxs, dcw, dcb, dlw, dlb = ops.cpe_branch_bwd(dl, dy, xs, cw, lw, c, lvl, wt, same)
+        return dx, dxs, dmod, dcw, dcb, dlw, dlb, dg, db, None, None, None, None
 
 
 class AdaSelfAttnFn(torch.autograd.Function):
@@ -261,41 +256,19 @@ class AdaSelfAttnFn(torch.autograd.Function):
 
     @_fwd
     def forward(ctx, x, mod, g, b, wqkv, bqkv, qnw, qnb, knw, knb, wp, bp, lvl, H, drop_p, seed, attn_p, dpath, bank, j):
-        N, C = x.shape
-        d = C // H
         n, mean, rstd = adaln_fwd(x, g, b, mod, lvl)
-        qkv, _ = ops.linear_fwd(n, wqkv, bqkv)
-        att = torch.empty(N, C, dtype=x.dtype, device=x.device)
-        lse = torch.empty(lvl.npad, H, dtype=torch.float32, device=x.device)
-        ops.attention_fwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles, lvl.n_self_tiles,
-                          (qnw, qnb), (knw, knb), att, lse, H, d, attn_p, mix_seed(seed, 1))
-        if dpath > 0.0:
-            br, _ = ops.linear_fwd(att, wp, bp, drop_p=drop_p, seed=seed)
-            y = ops.drop_path(br, x, dpath, mix_seed(seed, 5))
-        else:
-            y, _ = ops.linear_fwd(att, wp, bp, residual=x, drop_p=drop_p, seed=seed)
-        ctx.meta = (lvl, H, d, drop_p, seed, attn_p, float(dpath), bank, j)
+        y, qkv, att, lse = ops.selfattn_branch_fwd(n, x, wqkv, bqkv, (qnw, qnb), (knw, knb), wp, bp, lvl, H, drop_p, seed, attn_p, dpath)
+        ctx.meta = (lvl, H, drop_p, seed, attn_p, float(dpath), bank, j)
         ctx.save_for_backward(x, g, b, mod, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd)
         return y
 
     @_joined
     def backward(ctx, dy):
         x, g, b, mod, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd = ctx.saved_tensors
-        lvl, H, d, p, seed, attn_p, dpath, bank, j = ctx.meta
-        N, C = x.shape
+        lvl, H, p, seed, attn_p, dpath, bank, j = ctx.meta
         dy = dy.contiguous()
-        dyb = ops.drop_path(dy, None, dpath, mix_seed(seed, 5)) if dpath > 0.0 else dy
-        dz = ops.dropout(dyb, p, seed)
-        dwp, dbp = ops.linear_wgrad(dz, att)
-        datt = ops.linear_dgrad(dz, wp)
-        dqkv = torch.empty(N, 3 * C, dtype=x.dtype, device=x.device)
-        extra = torch.empty(max(lvl.n_extra, 1), 2 * C, dtype=x.dtype, device=x.device)
-        gq, bq, gk, bk = ops.attention_bwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles,
-                                           lvl.self_blocks, lvl.n_self_tiles, (qnw, qnb), (knw, knb), att, datt, lse, dqkv, 3 * C, 0,
-                                           dqkv, 3 * C, C, 2 * C, 0, 0, H, d, attn_p, mix_seed(seed, 1), lvl.kext, lvl.ext_pos,
-                                           lvl.n_extra, extra)
-        dwqkv, dbqkv = ops.linear_wgrad(dqkv, n)
-        dn = ops.linear_dgrad(dqkv, wqkv)
+        dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp = ops.selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, (qnw, qnb), (knw, knb), wp,
+                                                                             lvl, H, p, seed, attn_p, dpath, None)
         dmod = bank.grad_slice(j)
         dx, dg, db = adaln_bwd(dn, x, mean, rstd, g, b, mod, dmod, lvl, add=dy)
         return (dx, dmod, dg, db, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp) + (None,) * 8
@@ -307,12 +280,7 @@ class AdaFfnFn(torch.autograd.Function):
     @_fwd
     def forward(ctx, x, mod, g, b, w1, b1, w2, b2, lvl, drop_p, seed, dpath, bank, j):
         n, mean, rstd = adaln_fwd(x, g, b, mod, lvl)
-        a, hpre = ops.linear_fwd(n, w1, b1, act=ACT_GELU, save_pre=True, drop_p=drop_p, seed=seed)
-        if dpath > 0.0:
-            br, _ = ops.linear_fwd(a, w2, b2, drop_p=drop_p, seed=mix_seed(seed, 1))
-            y = ops.drop_path(br, x, dpath, mix_seed(seed, 5))
-        else:
-            y, _ = ops.linear_fwd(a, w2, b2, residual=x, drop_p=drop_p, seed=mix_seed(seed, 1))
+        y, a, hpre = ops.ffn_branch_fwd(n, x, w1, b1, w2, b2, drop_p, seed, dpath)
         ctx.meta = (lvl, drop_p, seed, float(dpath), bank, j)
         ctx.save_for_backward(x, g, b, mod, w1, w2, n, hpre, a, mean, rstd)
         return y
@@ -322,12 +290,7 @@ class AdaFfnFn(torch.autograd.Function):
         x, g, b, mod, w1, w2, n, hpre, a, mean, rstd = ctx.saved_tensors
         lvl, p, seed, dpath, bank, j = ctx.meta
         dy = dy.contiguous()
-        dyb = ops.drop_path(dy, None, dpath, mix_seed(seed, 5)) if dpath > 0.0 else dy
-        dz2 = ops.dropout(dyb, p, mix_seed(seed, 1))
-        dw2, db2 = ops.linear_wgrad(dz2, a)
-        dh = ops.linear_dgrad(dz2, w2, pre=hpre, act=ACT_GELU, drop_p=p, seed=seed)
-        dw1, db1 = ops.linear_wgrad(dh, n)
-        dn = ops.linear_dgrad(dh, w1)
+        dn, dw1, db1, dw2, db2 = ops.ffn_branch_bwd(dy, n, hpre, a, w1, w2, p, seed, dpath, None)
         dmod = bank.grad_slice(j)
         dx, dg, db = adaln_bwd(dn, x, mean, rstd, g, b, mod, dmod, lvl, add=dy)
         return (dx, dmod, dg, db, dw1, db1, dw2, db2) + (None,) * 6
@@ -498,88 +461,43 @@ def check_pdnorm_options(pdnorm_bn, pdnorm_ln, pdnorm_decouple, pdnorm_adaptive,
 
 class PointTransformerV3AdaNorm(PointTransformerV3CA):
     """PointTransformerV3(pdnorm_bn = pdnorm_ln = pdnorm_adaptive = True), model.py:864-1100: every stage a chain of Blocks.
-    forward(data_dict) takes data_dict["context"] = [B, pdnorm_context_channels], one vector per cloud.  The front end, its
-    prefetch, seeds and pack helpers are PointTransformerV3CA's."""
+    forward(data_dict) takes data_dict["context"] = [B, pdnorm_context_channels], one vector per cloud.  The constructor, the
+    forward prologue and the encoder / decoder walk, the front end, its prefetch, seeds and pack helpers are
+    PointTransformerV3CA's; this class supplies the PDNorm modules and the steps of a pass that run them."""
+    block_cls = AdaBlock
 
-    def __init__(self, in_channels=6, order=("z", "z-trans", "hilbert", "hilbert-trans"), stride=(2, 2, 2, 2),
-                 enc_depths=(2, 2, 2, 6, 2), enc_channels=(32, 64, 128, 256, 512), enc_num_head=(2, 4, 8, 16, 32),
-                 enc_patch_size=(1024,) * 5, dec_depths=(2, 2, 2, 2), dec_channels=(64, 64, 128, 256),
-                 dec_num_head=(4, 4, 8, 16), dec_patch_size=(1024,) * 4, mlp_ratio=4, ctx_channels=256,
-                 qkv_bias=True, qk_scale=None, qk_norm=False, attn_drop=0.0, proj_drop=0.0, drop_path=0.3,
-                 pre_norm=True, shuffle_orders=True, enable_rpe=False, enable_flash=True, upcast_attention=False,
-                 upcast_softmax=False, cls_mode=False, pdnorm_bn=True, pdnorm_ln=True, pdnorm_decouple=False,
-                 pdnorm_adaptive=True, pdnorm_context_channels=256, pdnorm_affine=True,
-                 pdnorm_conditions=("ScanNet", "S3DIS", "Structured3D"), pdnorm_only_decoder=False,
-                 add_coords_in_attn=False, scaled_cosine_attn=False):
-        nn.Module.__init__(self)
-        check_pdnorm_options(pdnorm_bn, pdnorm_ln, pdnorm_decouple, pdnorm_adaptive, pdnorm_affine, pdnorm_only_decoder)
-        unsupported = dict(enable_rpe=enable_rpe, cls_mode=cls_mode, scaled_cosine_attn=scaled_cosine_attn,
-                           not_flash=not enable_flash, not_qk_norm=not qk_norm, not_pre_norm=not pre_norm,
-                           no_qkv_bias=not qkv_bias, qk_scale=qk_scale is not None,
-                           add_coords=add_coords_in_attn not in (False, "none", None),
-                           depth_lt_1=any(d < 1 for d in list(enc_depths) + list(dec_depths)),
-                           stride_ne_2=any(s != 2 for s in stride),
-                           patch_ne_128=any(p > 128 for p in list(enc_patch_size) + list(dec_patch_size)))
-        bad = [k for k, v in unsupported.items() if v]
-        if bad:
-            raise NotImplementedError(f"lotus-hip builds the published 3D-LOTUS configuration family only; unsupported: {bad}")
-        if len(set(enc_patch_size) | set(dec_patch_size)) != 1:
-            raise NotImplementedError("all patch sizes must be equal")
-        ctx = int(pdnorm_context_channels)
-        self.context_channels = ctx
-        self.num_stages = len(enc_depths)
-        self.order = list(order)
-        self.shuffle_orders = shuffle_orders
-        self.proj_drop, self.attn_drop = float(proj_drop), float(attn_drop)
-        self.enc_channels, self.dec_channels = list(enc_channels), list(dec_channels) + [enc_channels[-1]]
-        self.enc_depths, self.dec_depths = [int(d) for d in enc_depths], [int(d) for d in dec_depths]
-        self.frontend = FrontEnd(self.num_stages, patch_size=enc_patch_size[0], orders=self.order,
-                                 n_patch_orders=max(self.enc_depths + self.dec_depths),
-                                 conv_widths=[max(e, d) for e, d in zip(self.enc_channels, self.dec_channels)])
-        ed = torch.linspace(0, drop_path, sum(self.enc_depths)).tolist()
-        dd = torch.linspace(0, drop_path, sum(self.dec_depths)).tolist() if self.dec_depths else []
-        self.enc_drop_path = [ed[sum(self.enc_depths[:s]):sum(self.enc_depths[:s + 1])] for s in range(self.num_stages)]
-        self.dec_drop_path = [list(reversed(dd[sum(self.dec_depths[:s]):sum(self.dec_depths[:s + 1])]))
-                              for s in range(self.num_stages - 1)]
+    def __init__(self, *args, pdnorm_bn=True, pdnorm_ln=True, pdnorm_decouple=False, pdnorm_adaptive=True, **kw):
+        super().__init__(*args, pdnorm_bn=pdnorm_bn, pdnorm_ln=pdnorm_ln, pdnorm_decouple=pdnorm_decouple,
+                         pdnorm_adaptive=pdnorm_adaptive, **kw)
 
-        self.embedding = _AdaEmbedding(in_channels, enc_channels[0], ctx)
-        self.enc = nn.Sequential()
-        for s in range(self.num_stages):
-            enc = nn.Sequential()
-            if s > 0:
-                enc.add_module("down", _AdaDown(enc_channels[s - 1], enc_channels[s], ctx))
-            for i in range(self.enc_depths[s]):
-                enc.add_module(f"block{i}", AdaBlock(enc_channels[s], enc_num_head[s], mlp_ratio, ctx))
-            self.enc.add_module(f"enc{s}", enc)
-        self.dec = nn.Sequential()
-        dc = self.dec_channels
-        for s in reversed(range(self.num_stages - 1)):
-            dec = nn.Sequential()
-            dec.add_module("up", _AdaUp(dc[s + 1], enc_channels[s], dc[s], ctx))
-            for i in range(self.dec_depths[s]):
-                dec.add_module(f"block{i}", AdaBlock(dc[s], dec_num_head[s], mlp_ratio, ctx))
-            self.dec.add_module(f"dec{s}", dec)
-        self._blocks = [m for m in self.modules() if isinstance(m, AdaBlock)]
-        self._block_level = {}
-        for s in range(self.num_stages):
-            for m in self.enc[s].children():
-                if isinstance(m, AdaBlock):
-                    self._block_level[id(m)] = s
-        for i, s in enumerate(reversed(range(self.num_stages - 1))):
-            for m in self.dec[i].children():
-                if isinstance(m, AdaBlock):
-                    self._block_level[id(m)] = s
+    # -- construction
+    @staticmethod
+    def _pdnorm_unsupported(*flags):
+        check_pdnorm_options(*flags)
+        return {}
+
+    @staticmethod
+    def _context_width(ctx_channels, pdnorm_context_channels):
+        return pdnorm_context_channels
+
+    def _make_embedding(self, cin, cout):
+        return _AdaEmbedding(cin, cout, self.context_channels)
+
+    def _make_down(self, cin, cout):
+        return _AdaDown(cin, cout, self.context_channels)
+
+    def _make_up(self, cin, cskip, cout):
+        return _AdaUp(cin, cskip, cout, self.context_channels)
+
+    def _add_depth(self, stage, i, c, h, mlp_ratio):
+        stage.add_module(f"block{i}", AdaBlock(c, h, mlp_ratio, self.context_channels))
+
+    def _index_sites(self):
         self._pdnorms = [m for m in self.modules() if isinstance(m, PDNorm)]  # slice j of the modulation bank = norm j
         self._pd_index = {id(m): j for j, m in enumerate(self._pdnorms)}
-        self._cablocks, self._cab_index, self._pair_params = [], {}, {}
-        self.kv_group = False
-        self._step = None
-        self._seed_base = None
-        self.order_perms = None
-        self._pending, self._deferred, self._fe_stream = None, None, None
+
+    def _drop_param_caches(self):
         self._nbt = None
-        self._sync_bn_checked = False
-        self.register_load_state_dict_post_hook(lambda m, _keys: setattr(m, "_step", None))
 
     def _check_sync_bn(self):
         """Data parallel (train_simple_policy.py:116-117,177): BatchNorm containers converted by
@@ -604,95 +522,54 @@ class PointTransformerV3AdaNorm(PointTransformerV3CA):
             wb += [lin.weight, lin.bias]
         return wb
 
-    def forward(self, data_dict, return_dec_layers=False):
-        feat, src, counts, ctx_counts, context = self._front_inputs(data_dict)
+    # -- the steps of a pass
+    def _check_inputs(self, feat, counts, context):
         if context is None or context.dim() != 2 or context.shape[0] != len(counts) or context.shape[1] != self.context_channels:
             raise ValueError(f"PointTransformerV3AdaNorm needs one context vector per cloud: [{len(counts)}, "
                              f"{self.context_channels}], got {None if context is None else tuple(context.shape)}")
         if context.dtype != torch.float32 or feat.dtype != torch.float32:
             raise NotImplementedError("SimplePolicyPTV3AdaNorm stores activations in fp32 only")
-        pend, self._pending = self._pending, None
-        if pend is not None and pend["pc_fts"] is src and pend["counts"] == list(counts):
-            levels = self.frontend.finish(pend, ctx_counts, need_coord=True)
-        else:
-            perms = self.order_perms if self.order_perms is not None else draw_order_perms(self.num_stages, self.shuffle_orders)
-            levels = self.frontend.build(src, counts, ctx_counts, perms, need_coord=True)
-        nxt, self._deferred = self._deferred, None
-        if nxt is not None:
-            nxt()
-        self.last_n_dup = levels[0].n_dup
-        training = self.training
-        if not self._sync_bn_checked:
-            self._check_sync_bn()
-        p = self.proj_drop if training else 0.0
-        pa = self.attn_drop if training else 0.0
-        base = self._seeds() if training else 0
-        self.last_seed = base
-        if training:
-            nbt = self._bn_counters()
-            if nbt:
-                torch._foreach_add_(nbt, 1)
-        site = 0
-        pid = self._pd_index
-        need = [b for b in self._blocks if not ops.conv_tap_active(levels[self._block_level[id(b)]], b.cpe[0].weight.shape[0])]
-        packs = dict(zip(need, ops.prepack_conv_weights([b.cpe[0].weight for b in need])))
-        for b in self._blocks:
-            packs.setdefault(b, ops.no_pack(feat.device))
-        n_ord = len(self.order)
 
-        bank = ModBank()
-        mods = ModAllFn.apply(context, bank, *self._mod_params())
+    def _begin(self, fw, data_dict, feat):
+        """Top of a pass -> stem output: the modulation bank of every PDNorm, the stem, then the join of the packed weights."""
+        fw.bank = ModBank()
+        fw.mods = ModAllFn.apply(fw.context, fw.bank, *self._mod_params())
         st = self.embedding.stem
-        nb = st.norm.norm
-        x = AdaStemFn.apply(feat, mods[pid[id(st.norm)]], st.conv.weight, nb.weight, nb.bias, nb.running_mean, nb.running_var,
-                            levels[0], training, bank, pid[id(st.norm)])
+        nb, j = st.norm.norm, self._pd_index[id(st.norm)]
+        x = AdaStemFn.apply(feat, fw.mods[j], st.conv.weight, nb.weight, nb.bias, nb.running_mean, nb.running_var,
+                            fw.levels[0], fw.training, fw.bank, j)
         ops.sync_side_stream()  # the packed convolution weights
+        return x
 
-        def run_block(blk, x, xs, lvl, si, dpath):
-            c0, c1, pc = blk.cpe[0], blk.cpe[1], blk.cpe[2]
-            x = AdaCpeFn.apply(x, xs, mods[pid[id(pc)]], c0.weight, c0.bias, c1.weight, c1.bias, pc.norm.weight, pc.norm.bias,
-                               lvl, packs[blk], bank, pid[id(pc)])
-            a, n1 = blk.attn, blk.norm1[0]
-            x = AdaSelfAttnFn.apply(x, mods[pid[id(n1)]], n1.norm.weight, n1.norm.bias, a.qkv.weight, a.qkv.bias, a.q_norm.weight,
-                                    a.q_norm.bias, a.k_norm.weight, a.k_norm.bias, a.proj.weight, a.proj.bias, lvl, blk.num_heads,
-                                    p, si, pa, dpath, bank, pid[id(n1)])
-            m, n2 = blk.mlp[0], blk.norm2[0]
-            return AdaFfnFn.apply(x, mods[pid[id(n2)]], n2.norm.weight, n2.norm.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight,
-                                  m.fc2.bias, lvl, p, mix_seed(si, 2), dpath, bank, pid[id(n2)])
+    def _enter_stage(self, fw, lvl):
+        pass
 
-        skips = []
-        for s in range(self.num_stages):
-            enc, lvl = self.enc[s], levels[s]
-            site += 1
-            seed = mix_seed(base, site)
-            if s > 0:
-                d = enc.down
-                pn = d.norm[0]
-                x = AdaPoolFn.apply(x, mods[pid[id(pn)]], d.proj.weight, d.proj.bias, pn.norm.weight, pn.norm.bias,
-                                    pn.norm.running_mean, pn.norm.running_var, lvl, training, bank, pid[id(pn)])
-            for i in range(self.enc_depths[s]):
-                si = seed if i == 0 else mix_seed(seed, 16 + i)
-                dpath = self.enc_drop_path[s][i] if training else 0.0
-                x = run_block(getattr(enc, f"block{i}"), x, x, lvl.for_order(i % n_ord), si, dpath)
-            skips.append(x)
-        outs = [self._pack(x, levels[-1])]
-        for i, s in enumerate(reversed(range(self.num_stages - 1))):
-            dec, lvl, child = self.dec[i], levels[s], levels[s + 1]
-            site += 1
-            seed = mix_seed(base, site)
-            u, us = dec.up.proj, dec.up.proj_skip
-            nu, ns = u[1], us[1]
-            x, skip = AdaUnpoolFn.apply(x, skips[s], mods[pid[id(nu)]], mods[pid[id(ns)]], u[0].weight, u[0].bias, nu.norm.weight,
-                                        nu.norm.bias, nu.norm.running_mean, nu.norm.running_var, us[0].weight, us[0].bias,
-                                        ns.norm.weight, ns.norm.bias, ns.norm.running_mean, ns.norm.running_var, child, lvl,
-                                        training, bank, pid[id(nu)], pid[id(ns)])
-            for j in range(self.dec_depths[s]):
-                si = seed if j == 0 else mix_seed(seed, 16 + j)
-                dpath = self.dec_drop_path[s][j] if training else 0.0
-                # the first Block of a decoder stage convolves the proj_skip branch (its sparse_conv_feat), SURVEY.md Trap 3
-                x = run_block(getattr(dec, f"block{j}"), x, skip if j == 0 else x, lvl.for_order(j % n_ord), si, dpath)
-            outs.append(self._pack(x, lvl))
-        return outs if return_dec_layers else outs[-1]
+    def _pool(self, fw, d, x, lvl):
+        pn = d.norm[0]
+        j = self._pd_index[id(pn)]
+        return AdaPoolFn.apply(x, fw.mods[j], d.proj.weight, d.proj.bias, pn.norm.weight, pn.norm.bias, pn.norm.running_mean,
+                               pn.norm.running_var, lvl, fw.training, fw.bank, j)
+
+    def _unpool(self, fw, up, x, skip, child, lvl):
+        u, us = up.proj, up.proj_skip
+        nu, ns = u[1], us[1]
+        ju, js = self._pd_index[id(nu)], self._pd_index[id(ns)]
+        return AdaUnpoolFn.apply(x, skip, fw.mods[ju], fw.mods[js], u[0].weight, u[0].bias, nu.norm.weight, nu.norm.bias,
+                                 nu.norm.running_mean, nu.norm.running_var, us[0].weight, us[0].bias, ns.norm.weight,
+                                 ns.norm.bias, ns.norm.running_mean, ns.norm.running_var, child, lvl, fw.training, fw.bank, ju, js)
+
+    def _run_depth(self, fw, stage, i, x, xs, lvl_o, lvl, si, dpath):
+        blk, mods, bank, pid, p = getattr(stage, f"block{i}"), fw.mods, fw.bank, self._pd_index, fw.p
+        c0, c1, pc = blk.cpe[0], blk.cpe[1], blk.cpe[2]
+        x = AdaCpeFn.apply(x, xs, mods[pid[id(pc)]], c0.weight, c0.bias, c1.weight, c1.bias, pc.norm.weight, pc.norm.bias,
+                           lvl_o, fw.packs[blk], bank, pid[id(pc)])
+        a, n1 = blk.attn, blk.norm1[0]
+        x = AdaSelfAttnFn.apply(x, mods[pid[id(n1)]], n1.norm.weight, n1.norm.bias, a.qkv.weight, a.qkv.bias, a.q_norm.weight,
+                                a.q_norm.bias, a.k_norm.weight, a.k_norm.bias, a.proj.weight, a.proj.bias, lvl_o, blk.num_heads,
+                                p, si, fw.pa, dpath, bank, pid[id(n1)])
+        m, n2 = blk.mlp[0], blk.norm2[0]
+        return AdaFfnFn.apply(x, mods[pid[id(n2)]], n2.norm.weight, n2.norm.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight,
+                              m.fc2.bias, lvl_o, p, mix_seed(si, 2), dpath, bank, pid[id(n2)])
 
 
 def cloud_context(txt_ctx, txt_w, lens):

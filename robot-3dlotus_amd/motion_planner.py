@@ -12,7 +12,6 @@ heatmap cross entropy are lotus-hip kernels (ops.*Fn); the [B, T]-sized rotation
 trajectory-embedding bias (5 x 64 floats) and the effective stem weight (see prepare_ptv3_batch) are a few ATen
 launches on small tensors.
 """
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -122,9 +121,7 @@ class MotionPlannerPTV3CA(BaseModel):
 
     def _forward(self, batch, compute_loss=False, **kwargs):
         batch = self.prepare_batch(batch)
-        dev = batch["pc_fts"].device
-        if dev.type != "cuda":
-            raise RuntimeError("lotus-hip runs on a HIP device only (no CPU fallback); move the model and batch to cuda")
+        dev = self.hip_device(batch)
         act, head = self.config.action_config, self.act_proj_head
         last = self.ptv3_model(self.prepare_ptv3_batch(batch), return_dec_layers=True)[-1]
         x, lvl = last.feat, last.level
@@ -157,19 +154,13 @@ class MotionPlannerPTV3CA(BaseModel):
             return None, losses                                  # trainer discards the actions (see policy.py)
         if decode:   # :238-267, best_disc_pos == 'max'; one launch pair per step instead of B*T host round trips
             pcf = batch["pc_fts"] if batch["pc_fts"].stride(1) == 1 else batch["pc_fts"].contiguous()
-            best = act.get("best_disc_pos", "max")   # motion_planner_ptv3.py:263
-            if best == "ens1":
-                cnts = list(batch["npoints_in_batch"])
-                pos = torch.stack([ops.pos_decode_ens1(xt.detach(), pcf, cnts, nb, act.pos_bin_size) for xt in xts], 1)
-            else:
-                pos = torch.stack([ops.pos_decode_max(xt.detach(), pcf, lvl.off, B, nb, act.pos_bin_size) for xt in xts], 1)
+            best = act.get("best_disc_pos", "max")
+            pos = torch.stack([self.decode_disc_pos(best, xt.detach(), pcf, batch["npoints_in_batch"], lvl, nb, act.pos_bin_size)
+                               for xt in xts], 1)
             pos = pos.float()                                    # reference: .float() at :266
         else:
             pos = batch["gt_trajs"][..., :3].float()
-        from scipy.spatial.transform import Rotation as R
-        rot_bins = torch.argmax(pred_rot.reshape(B * T, eb, 3), 1).cpu().numpy()
-        quat = np.stack([R.from_euler("xyz", r * head.euler_resolution - 180, degrees=True).as_quat() for r in rot_bins], 0)
-        quat = torch.from_numpy(quat).to(dev).reshape(B, T, 4)
+        quat = self.decode_euler_disc(pred_rot.reshape(B * T, eb, 3), head.euler_resolution, dev).reshape(B, T, 4)
         final = torch.cat([pos, quat, pred_open.detach().unsqueeze(-1), pred_stop.detach().unsqueeze(-1)], -1)
         return (final, losses) if compute_loss else final
 

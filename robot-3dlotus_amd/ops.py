@@ -1035,6 +1035,86 @@ def _side_ctx(dev, ws_side_bytes, reads, rows=0):
 
 
 # ------------------------------------------------------------------------------------ sub-blocks
+# Per-launch bodies of the three Block sub-blocks WITHOUT their norm: the part the plain-LayerNorm nodes below (their
+# per-launch branches) and the PDNorm nodes of adanorm.py share.  The caller passes the weights it uses (bf16 shadows here, the
+# parameters there) and runs its own norm forward / backward around them.
+def cpe_branch_fwd(xs, cw, cb, lw, lb, lvl, wt):
+    """-> (c, l) = SubMConv3d_3(xs), Linear(c): the input of the sub-block's norm, and what its backward needs."""
+    c = conv_fwd(xs, cw, cb, lvl.nbr27, lvl.order[0], w_t=wt, tap_plan=lvl.tap_plan)
+    l, _ = linear_fwd(c, lw, lb)
+    return c, l
+
+
+def cpe_branch_bwd(dl, dy, xs, cw, lw, c, lvl, wt, same):
+    """dl = the norm's input gradient, dy = the node's -> (dx, dxs | None, dcw, dcb, dlw, dlb)."""
+    dlw, dlb = linear_wgrad(dl, c)
+    dc = linear_dgrad(dl, lw)
+    dcw, dcb = conv_wgrad(dc, xs, cw.shape, lvl.nbr27)
+    if same:  # d x = dy (residual) + conv dgrad
+        dx = conv_dgrad(dc, cw, lvl.nbr27, lvl.order[0], add=dy, w_t=wt, lvl=lvl, tap_plan=lvl.tap_plan)
+        return dx, None, dcw, dcb, dlw, dlb
+    dxs = conv_dgrad(dc, cw, lvl.nbr27, lvl.order[0], w_t=wt, lvl=lvl, tap_plan=lvl.tap_plan)
+    return dy, dxs, dcw, dcb, dlw, dlb
+
+
+def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, attn_p, dpath):
+    """n = norm(x) -> (y, qkv, att, lse), y = x + DropPath(drop(proj(PatchAttention(qkv(n))))); qn / kn = (weight, bias)."""
+    N, C = x.shape
+    qkv, _ = linear_fwd(n, wqkv, bqkv)
+    att = torch.empty(N, C, dtype=x.dtype, device=x.device)
+    lse = torch.empty(lvl.npad, H, dtype=torch.float32, device=x.device)
+    attention_fwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles,
+                  lvl.n_self_tiles, qn, kn, att, lse, H, C // H, attn_p, mix_seed(seed, 1))
+    if dpath > 0.0:
+        br, _ = linear_fwd(att, wp, bp, drop_p=drop_p, seed=seed)
+        y = drop_path(br, x, dpath, mix_seed(seed, 5))
+    else:
+        y, _ = linear_fwd(att, wp, bp, residual=x, drop_p=drop_p, seed=seed)
+    return y, qkv, att, lse
+
+
+def selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, qn, kn, wp, lvl, H, p, seed, attn_p, dpath, hand):
+    """-> (dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp); `hand`: the hand-over that may hold dy pre-masked (or None)."""
+    N, C = n.shape
+    dyb = drop_path(dy, None, dpath, mix_seed(seed, 5)) if dpath > 0.0 else dy
+    dz = _masked(dyb, p, seed, hand)
+    dwp, dbp = linear_wgrad(dz, att)
+    datt = linear_dgrad(dz, wp)
+    # every (point, q|k|v column) is written exactly once by its owner position; the k/v gradients of the
+    # borrowed tail-patch copies go to a small side buffer and are added afterwards (no atomics, no memset)
+    dqkv = torch.empty(N, 3 * C, dtype=n.dtype, device=n.device)
+    extra = torch.empty(max(lvl.n_extra, 1), 2 * C, dtype=n.dtype, device=n.device)
+    gq, bq, gk, bk = attention_bwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner,
+                                   lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, qn, kn, att,
+                                   datt, lse, dqkv, 3 * C, 0, dqkv, 3 * C, C, 2 * C, 0, 0, H, C // H, attn_p, mix_seed(seed, 1),
+                                   lvl.kext, lvl.ext_pos, lvl.n_extra, extra)
+    dwqkv, dbqkv = linear_wgrad(dqkv, n)
+    dn = linear_dgrad(dqkv, wqkv)
+    return dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp
+
+
+def ffn_branch_fwd(n, x, w1, b1, w2, b2, drop_p, seed, dpath):
+    """n = norm(x) -> (y, a, hpre), y = x + DropPath(drop(fc2(a))), a = drop(GELU(hpre)), hpre = fc1(n)."""
+    a, hpre = linear_fwd(n, w1, b1, act=ACT_GELU, save_pre=True, drop_p=drop_p, seed=seed)
+    if dpath > 0.0:
+        br, _ = linear_fwd(a, w2, b2, drop_p=drop_p, seed=mix_seed(seed, 1))
+        y = drop_path(br, x, dpath, mix_seed(seed, 5))
+    else:
+        y, _ = linear_fwd(a, w2, b2, residual=x, drop_p=drop_p, seed=mix_seed(seed, 1))
+    return y, a, hpre
+
+
+def ffn_branch_bwd(dy, n, hpre, a, w1, w2, p, seed, dpath, hand):
+    """-> (dn, dw1, db1, dw2, db2); `hand` as in selfattn_branch_bwd."""
+    dyb = drop_path(dy, None, dpath, mix_seed(seed, 5)) if dpath > 0.0 else dy
+    dz2 = _masked(dyb, p, mix_seed(seed, 1), hand)
+    dw2, db2 = linear_wgrad(dz2, a)
+    dh = linear_dgrad(dz2, w2, pre=hpre, act=ACT_GELU, drop_p=p, seed=seed)
+    dw1, db1 = linear_wgrad(dh, n)
+    dn = linear_dgrad(dh, w1)
+    return dn, dw1, db1, dw2, db2
+
+
 class CpeFn(torch.autograd.Function):
     """x1 = x + LN(Linear(SubMConv3d_3(xs))).  In the encoder xs is x; in the decoder xs is the
     stale proj_skip branch (SURVEY.md Trap 3), hence two tensor inputs."""
@@ -1059,8 +1139,7 @@ class CpeFn(torch.autograd.Function):
                            ws.numel(), wc, wc.numel(), _counters(x.device), _capi.stream_ptr())
             ctx.save_for_backward(xs, cw, lw, g, saved, wt)
             return y
-        c = conv_fwd(xs, cw, cb, lvl.nbr27, lvl.order[0], w_t=wt, tap_plan=lvl.tap_plan)
-        l, _ = linear_fwd(c, lwk, lb)
+        c, l = cpe_branch_fwd(xs, cw, cb, lwk, lb, lvl, wt)
         y, mean, rstd = ln_fwd(l, g, b, res=x)
         ctx.save_for_backward(xs, cw, lw, g, c, l, mean, rstd, wt)
         return y
@@ -1093,14 +1172,7 @@ class CpeFn(torch.autograd.Function):
             return dy, dxc, dcw, dcb, dlw, dlb, dg, db, None, None
         xs, cw, lw, g, c, l, mean, rstd, wt = ctx.saved_tensors
         dl, dg, db = ln_bwd(dy, l, mean, rstd, g)
-        dlw, dlb = linear_wgrad(dl, c)
-        dc = linear_dgrad(dl, ctx.wk[0])
-        dcw, dcb = conv_wgrad(dc, xs, cw.shape, lvl.nbr27)
-        if ctx.same:  # d x = dy (residual) + conv dgrad
-            dx = conv_dgrad(dc, cw, lvl.nbr27, lvl.order[0], add=dy, w_t=wt, lvl=lvl, tap_plan=lvl.tap_plan)
-            return dx, None, dcw, dcb, dlw, dlb, dg, db, None, None
-        dxs = conv_dgrad(dc, cw, lvl.nbr27, lvl.order[0], w_t=wt, lvl=lvl, tap_plan=lvl.tap_plan)
-        return dy, dxs, dcw, dcb, dlw, dlb, dg, db, None, None
+        return cpe_branch_bwd(dl, dy, xs, cw, ctx.wk[0], c, lvl, wt, ctx.same) + (dg, db, None, None)
 
 
 class FfnFn(torch.autograd.Function):
@@ -1132,12 +1204,7 @@ class FfnFn(torch.autograd.Function):
             ctx.save_for_backward(x, g, w1, w2, saved)
             return y
         n, mean, rstd = ln_fwd(x, g, b)
-        a, hpre = linear_fwd(n, w1k, b1, act=ACT_GELU, save_pre=True, drop_p=drop_p, seed=seed)
-        if dpath > 0.0:
-            br, _ = linear_fwd(a, w2k, b2, drop_p=drop_p, seed=mix_seed(seed, 1))
-            y = drop_path(br, x, dpath, mix_seed(seed, 5))
-        else:
-            y, _ = linear_fwd(a, w2k, b2, residual=x, drop_p=drop_p, seed=mix_seed(seed, 1))
+        y, a, hpre = ffn_branch_fwd(n, x, w1k, b1, w2k, b2, drop_p, seed, dpath)
         ctx.save_for_backward(x, g, w1, w2, n, hpre, a, mean, rstd)
         return y
 
@@ -1170,12 +1237,7 @@ class FfnFn(torch.autograd.Function):
             return (dx, grads[:C], grads[_al4(C):_al4(C) + C], grads[o1:o1 + Hd * C].view(Hd, C), grads[o1 + Hd * C:o1 + Hd * C + Hd],
                     grads[o2:o2 + C * Hd].view(C, Hd), grads[o2 + C * Hd:o2 + C * Hd + C], None, None, None, None, None)
         x, g, w1, w2, n, hpre, a, mean, rstd = ctx.saved_tensors
-        dyb = drop_path(dy, None, ctx.dpath, mix_seed(seed, 5)) if ctx.dpath > 0.0 else dy
-        dz2 = _masked(dyb, p, mix_seed(seed, 1), hand_in)
-        dw2, db2 = linear_wgrad(dz2, a)
-        dh = linear_dgrad(dz2, ctx.wk[1], pre=hpre, act=ACT_GELU, drop_p=p, seed=seed)
-        dw1, db1 = linear_wgrad(dh, n)
-        dn = linear_dgrad(dh, ctx.wk[0])
+        dn, dw1, db1, dw2, db2 = ffn_branch_bwd(dy, n, hpre, a, ctx.wk[0], ctx.wk[1], p, seed, ctx.dpath, hand_in)
         dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy, hand=hand_out)
         return dx, dg, db, dw1, db1, dw2, db2, None, None, None, None, None
 
@@ -1208,16 +1270,7 @@ class SelfAttnFn(torch.autograd.Function):
             ctx.save_for_backward(x, g, wqkv, qnw, qnb, knw, knb, wp, saved)
             return y
         n, mean, rstd = ln_fwd(x, g, b)
-        qkv, _ = linear_fwd(n, wqkvk, bqkv)
-        att = torch.empty(N, C, dtype=x.dtype, device=x.device)
-        lse = torch.empty(lvl.npad, H, dtype=torch.float32, device=x.device)
-        attention_fwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles,
-                      lvl.n_self_tiles, (qnw, qnb), (knw, knb), att, lse, H, d, attn_p, mix_seed(seed, 1))
-        if dpath > 0.0:
-            br, _ = linear_fwd(att, wpk, bp, drop_p=drop_p, seed=seed)
-            y = drop_path(br, x, dpath, mix_seed(seed, 5))
-        else:
-            y, _ = linear_fwd(att, wpk, bp, residual=x, drop_p=drop_p, seed=seed)
+        y, qkv, att, lse = selfattn_branch_fwd(n, x, wqkvk, bqkv, (qnw, qnb), (knw, knb), wpk, bp, lvl, H, drop_p, seed, attn_p, dpath)
         ctx.save_for_backward(x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd)
         return y
 
@@ -1249,21 +1302,8 @@ class SelfAttnFn(torch.autograd.Function):
                     grads[o2 + 2 * d4:o2 + 2 * d4 + d], grads[o2 + 3 * d4:o2 + 3 * d4 + d], grads[o3:o3 + C * C].view(C, C),
                     grads[o3 + C * C:o3 + C * C + C], None, None, None, None, None, None, None)
         x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd = ctx.saved_tensors
-        N, C = x.shape
-        dyb = drop_path(dy, None, ctx.dpath, mix_seed(seed, 5)) if ctx.dpath > 0.0 else dy
-        dz = _masked(dyb, p, seed, ctx.hand_in)
-        dwp, dbp = linear_wgrad(dz, att)
-        datt = linear_dgrad(dz, ctx.wk[1])
-        # every (point, q|k|v column) is written exactly once by its owner position; the k/v gradients of the
-        # borrowed tail-patch copies go to a small side buffer and are added afterwards (no atomics, no memset)
-        dqkv = torch.empty(N, 3 * C, dtype=x.dtype, device=x.device)
-        extra = torch.empty(max(lvl.n_extra, 1), 2 * C, dtype=x.dtype, device=x.device)
-        gq, bq, gk, bk = attention_bwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner,
-                                       lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, (qnw, qnb), (knw, knb), att,
-                                       datt, lse, dqkv, 3 * C, 0, dqkv, 3 * C, C, 2 * C, 0, 0, H, d, attn_p, mix_seed(seed, 1),
-                                       lvl.kext, lvl.ext_pos, lvl.n_extra, extra)
-        dwqkv, dbqkv = linear_wgrad(dqkv, n)
-        dn = linear_dgrad(dqkv, ctx.wk[0])
+        dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp = selfattn_branch_bwd(dy, n, qkv, att, lse, ctx.wk[0], (qnw, qnb), (knw, knb),
+                                                                         ctx.wk[1], lvl, H, p, seed, attn_p, ctx.dpath, ctx.hand_in)
         dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy)
         return dx, dg, db, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, None, None, None, None, None, None, None
 

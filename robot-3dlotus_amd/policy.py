@@ -61,6 +61,34 @@ class BaseModel(nn.Module):
             out = out.index_copy(0, pos_j, t.to(ctx.dtype))
         return out, [c + ne for c in ctx_counts]
 
+    @staticmethod
+    def hip_device(batch):
+        dev = batch["pc_fts"].device
+        if dev.type != "cuda":
+            raise RuntimeError("lotus-hip runs on a HIP device only (no CPU fallback); move the model and batch to cuda")
+        return dev
+
+    @staticmethod
+    def decode_disc_pos(best, xt, pc, counts, lvl, nb, bin_size):
+        """get_best_pos_from_disc_pos (utils/action_position_utils.py:48-85) of the logits xt [N, 3 * nb] for every cloud:
+        f64 [B, 3].  best = action_config.best_disc_pos (simple_policy_ptv3.py:266, motion_planner_ptv3.py:263; set by the
+        evaluation scripts); pc = pc_fts with unit column stride."""
+        if best == "ens1":
+            return ops.pos_decode_ens1(xt, pc, list(counts), nb, bin_size)
+        if best == "max":
+            return ops.pos_decode_max(xt, pc, lvl.off, len(lvl.counts), nb, bin_size)  # one launch pair
+        raise ValueError(f"best_disc_pos must be 'max' or 'ens1', got {best!r}")
+
+    @staticmethod
+    def decode_euler_disc(rot_logits, resolution, dev):
+        """euler_disc decode, simple_policy_ptv3.py:292-296 (float64 on purpose): arg-max bin per axis of
+        rot_logits [M, bins, 3] -> scipy 'xyz' quaternions, f64 [M, 4] on `dev`."""
+        from scipy.spatial.transform import Rotation as R
+
+        rot_bins = torch.argmax(rot_logits, 1).cpu().numpy()
+        quat = np.stack([R.from_euler("xyz", x * resolution - 180, degrees=True).as_quat() for x in rot_bins], 0)
+        return torch.from_numpy(quat).to(dev)
+
     def _init_weights(self, m):
         if isinstance(m, nn.Linear):
             nn.init.trunc_normal_(m.weight, std=0.02)
@@ -138,10 +166,10 @@ class SimplePolicyPTV3CA(BaseModel):
         super().__init__()
         config = to_cfg(config)
         self.config = config
-        p3 = {k: v for k, v in config.ptv3_config.items() if k in _PTV3_KEYS}
-        self.ptv3_model = PointTransformerV3CA(**p3)
         act = config.action_config
+        self.ptv3_model = self._make_backbone({k: v for k, v in config.ptv3_config.items() if k in _PTV3_KEYS}, act)
         self.txt_fc = nn.Linear(act.txt_ft_size, act.context_channels)
+        self._add_txt_reduce(act)
         if act.use_ee_pose:     # simple_policy_ptv3.py:386-389 (the published v1 model sets both to False)
             self.pose_embedding = RobotPoseEmbedding(act.context_channels)
         if act.use_step_id:
@@ -150,6 +178,12 @@ class SimplePolicyPTV3CA(BaseModel):
                                         config.ptv3_config.dec_channels[0], act.dim_actions, dropout=act.dropout,
                                         voxel_size=act.voxel_size, pos_bins=act.pos_bins)
         self.apply(self._init_weights)
+
+    def _make_backbone(self, p3, act):
+        return PointTransformerV3CA(**p3)
+
+    def _add_txt_reduce(self, act):
+        """Layers of the instruction reduction, registered between txt_fc and the pose / step embeddings (none here)."""
 
     # -- reference API ---------------------------------------------------------------------
     def prepare_ptv3_batch(self, batch):
@@ -237,6 +271,9 @@ class SimplePolicyPTV3CA(BaseModel):
             return self._forward(batch, compute_loss, **kwargs)
 
     def _forward(self, batch, compute_loss=False, **kwargs):
+        """simple_policy_ptv3.py:238-306: backbone, head + losses as one node (ops.HeadLossFn for the published head, ops.RegHeadLossFn
+        for a head with a regression option: pos_pred_type 'heatmap_mlp' and / or rot_pred_type 'euler' / 'quat'), then the
+        reference's decode."""
         batch = self.prepare_batch(batch)
         up = batch.pop("_upload_stream", None)
         if up is not None:  # uploaded by prefetch() on the front-end stream: order this stream after it, tell the allocator
@@ -245,78 +282,7 @@ class SimplePolicyPTV3CA(BaseModel):
             for v in batch.values():
                 if isinstance(v, torch.Tensor) and v.is_cuda:
                     v.record_stream(cur)
-        dev = batch["pc_fts"].device
-        if dev.type != "cuda":
-            raise RuntimeError("lotus-hip runs on a HIP device only (no CPU fallback); move the model and batch to cuda")
-        act, head = self.config.action_config, self.act_proj_head
-        if not head.published:
-            return self._forward_reg(batch, compute_loss, **kwargs)
-        outs = self.ptv3_model(self.prepare_ptv3_batch(batch), return_dec_layers=True)
-        last = outs[-1]
-        lvl = last.level
-        B = len(lvl.counts)
-        gt = batch["gt_actions"].float().contiguous() if "gt_actions" in batch else None
-        tgt = None
-        with_loss = bool(compute_loss)
-        if with_loss:
-            dp = batch.get("disc_pos_probs")
-            if dp is None:
-                # no host-made soft labels in the batch: build them on the device from the ground-truth positions
-                # (get_disc_gt_pos_prob, utils/action_position_utils.py:7-46; the dataset would otherwise ship
-                # 3 * n * 2 * pos_bins floats per cloud over PCIe).  Options of the reference dataset
-                # (simple_policy_dataset.py:41-42): batch["pos_heatmap_type"] 'plain' | 'dist', and
-                # batch["robot_point_mask"] (bool [N]) for pos_heatmap_no_robot.
-                pc = batch["pc_fts"] if batch["pc_fts"].stride(1) == 1 else batch["pc_fts"].contiguous()
-                tgt = ops.pos_targets(pc, lvl.off, lvl.batch, gt, 2 * head.pos_bins, act.pos_bin_size,
-                                      batch.get("pos_heatmap_type", "plain"), batch.get("robot_point_mask"))
-            else:
-                tgt = dp if isinstance(dp, torch.Tensor) else torch.cat([t.reshape(-1) for t in dp]).to(dev)
-                tgt = tgt.float().contiguous()
-        hm, am = head.heatmap_mlp, head.action_mlp
-        p = head.dropout if self.training else 0.0
-        lc = self.config.loss_config
-        dummy = last.feat.new_zeros(1)
-        losses, xt, ae = ops.HeadLossFn.apply(
-            last.feat, hm[0].weight, hm[0].bias, hm[3].weight, hm[3].bias, am[0].weight, am[0].bias, am[3].weight,
-            am[3].bias, lvl, tgt if with_loss else dummy, gt if gt is not None else dummy.view(1, 1),
-            float(lc.pos_weight), float(lc.rot_weight), p, ops.mix_seed(self.ptv3_model.last_seed, 1000), with_loss)
-        nb = 2 * head.pos_bins
-        pred_pos = xt.view(-1, 3, nb).permute(1, 0, 2)          # (3, N, 2*pos_bins) like the reference
-        pred_rot = ae[:, :head.euler_bins * 3].view(B, head.euler_bins, 3)
-        pred_open = ae[:, -1]
-        self.last_pred = (pred_pos, pred_rot, pred_open)
-
-        decode = kwargs.get("compute_final_action", True)
-        if compute_loss and self.training and not decode and not kwargs.get("decode_actions", False):
-            # Training step of the reference trainer (`_, losses = model(batch, compute_loss=True,
-            # compute_final_action=False)`, train_simple_policy.py:211): the action tuple is discarded, so
-            # the device->host argmax copy + per-sample scipy decode (simple_policy_ptv3.py:292-296) is
-            # skipped unless decode_actions=True is passed.  See INTEGRATION.md.
-            return None, {"pos": losses[0], "rot": losses[1], "open": losses[2], "total": losses[3]}
-        if decode:
-            pc = batch["pc_fts"] if batch["pc_fts"].stride(1) == 1 else batch["pc_fts"].contiguous()
-            best = act.get("best_disc_pos", "max")   # simple_policy_ptv3.py:266 (set by the evaluation scripts)
-            if best == "ens1":
-                pos = ops.pos_decode_ens1(xt, pc, list(batch["npoints_in_batch"]), nb, act.pos_bin_size)
-            elif best == "max":
-                pos = ops.pos_decode_max(xt, pc, lvl.off, B, nb, act.pos_bin_size)  # f64 [B, 3], one launch pair
-            else:
-                raise ValueError(f"best_disc_pos must be 'max' or 'ens1', got {best!r}")
-        else:
-            pos = gt[..., :3]
-        # euler_disc decode, simple_policy_ptv3.py:292-296 (float64 on purpose)
-        from scipy.spatial.transform import Rotation as R
-        rot_bins = torch.argmax(pred_rot, 1).cpu().numpy()
-        quat = np.stack([R.from_euler("xyz", x * head.euler_resolution - 180, degrees=True).as_quat() for x in rot_bins], 0)
-        final = torch.cat([pos.double(), torch.from_numpy(quat).to(dev), pred_open.detach().double().unsqueeze(-1)], -1)
-        if compute_loss:
-            return final, {"pos": losses[0], "rot": losses[1], "open": losses[2], "total": losses[3]}
-        return final
-
-    def _forward_reg(self, batch, compute_loss=False, **kwargs):
-        """The head with a regression option (pos_pred_type 'heatmap_mlp' and / or rot_pred_type 'euler' / 'quat'),
-        simple_policy_ptv3.py:238-306: ops.RegHeadLossFn, then the reference's decode.  `batch` is prepared already."""
-        dev = batch["pc_fts"].device
+        dev = self.hip_device(batch)
         act, head = self.config.action_config, self.act_proj_head
         mlp = head.pos_pred_type == "heatmap_mlp"
         outs = self.ptv3_model(self.prepare_ptv3_batch(batch), return_dec_layers=True)
@@ -326,15 +292,19 @@ class SimplePolicyPTV3CA(BaseModel):
         gt = batch["gt_actions"].float().contiguous() if "gt_actions" in batch else None
         with_loss = bool(compute_loss)
         ga = 8 if head.rot_pred_type == "quat" else 7
-        if with_loss and (gt is None or gt.shape[-1] != ga):
+        if not head.published and with_loss and (gt is None or gt.shape[-1] != ga):
             raise ValueError(f"rot_pred_type={head.rot_pred_type!r} takes gt_actions [B, {ga}], got "
                              f"{None if gt is None else tuple(gt.shape)}")
         pc = batch["pc_fts"] if batch["pc_fts"].stride(1) == 1 else batch["pc_fts"].contiguous()
-        pc = pc.float()
         tgt = None
         if with_loss and not mlp:
             dp = batch.get("disc_pos_probs")
             if dp is None:
+                # no host-made soft labels in the batch: build them on the device from the ground-truth positions
+                # (get_disc_gt_pos_prob, utils/action_position_utils.py:7-46; the dataset would otherwise ship
+                # 3 * n * 2 * pos_bins floats per cloud over PCIe).  Options of the reference dataset
+                # (simple_policy_dataset.py:41-42): batch["pos_heatmap_type"] 'plain' | 'dist', and
+                # batch["robot_point_mask"] (bool [N]) for pos_heatmap_no_robot.
                 tgt = ops.pos_targets(pc, lvl.off, lvl.batch, gt, 2 * head.pos_bins, act.pos_bin_size,
                                       batch.get("pos_heatmap_type", "plain"), batch.get("robot_point_mask"))
             else:
@@ -344,41 +314,45 @@ class SimplePolicyPTV3CA(BaseModel):
         p = head.dropout if self.training else 0.0
         lc = self.config.loss_config
         dummy = last.feat.new_zeros(1)
-        losses, xt, rot, pred_open = ops.RegHeadLossFn.apply(
-            last.feat, hm[0].weight, hm[0].bias, hm[3].weight, hm[3].bias, am[0].weight, am[0].bias, am[3].weight,
-            am[3].bias, lvl, tgt if tgt is not None else dummy, gt if with_loss else dummy.view(1, 1), pc,
-            head.pos_pred_type, head.rot_pred_type, float(act.get("pos_heatmap_temp", 1)), float(lc.pos_weight),
-            float(lc.rot_weight), p, ops.mix_seed(self.ptv3_model.last_seed, 1000), with_loss)
+        if head.published:
+            losses, xt, rot = ops.HeadLossFn.apply(
+                last.feat, hm[0].weight, hm[0].bias, hm[3].weight, hm[3].bias, am[0].weight, am[0].bias, am[3].weight,
+                am[3].bias, lvl, tgt if with_loss else dummy, gt if gt is not None else dummy.view(1, 1),
+                float(lc.pos_weight), float(lc.rot_weight), p, ops.mix_seed(self.ptv3_model.last_seed, 1000), with_loss)
+            pred_open = rot[:, -1]
+        else:
+            losses, xt, rot, pred_open = ops.RegHeadLossFn.apply(
+                last.feat, hm[0].weight, hm[0].bias, hm[3].weight, hm[3].bias, am[0].weight, am[0].bias, am[3].weight,
+                am[3].bias, lvl, tgt if tgt is not None else dummy, gt if with_loss else dummy.view(1, 1), pc.float(),
+                head.pos_pred_type, head.rot_pred_type, float(act.get("pos_heatmap_temp", 1)), float(lc.pos_weight),
+                float(lc.rot_weight), p, ops.mix_seed(self.ptv3_model.last_seed, 1000), with_loss)
         nb = 2 * head.pos_bins
-        pred_pos = xt if mlp else xt.view(-1, 3, nb).permute(1, 0, 2)
+        pred_pos = xt if mlp else xt.view(-1, 3, nb).permute(1, 0, 2)          # (3, N, 2*pos_bins) like the reference
         pred_rot = rot[:, :head.euler_bins * 3].view(B, head.euler_bins, 3) if head.rot_pred_type == "euler_disc" else rot
         self.last_pred = (pred_pos, pred_rot, pred_open)
         loss_dict = {"pos": losses[0], "rot": losses[1], "open": losses[2], "total": losses[3]}
 
         decode = kwargs.get("compute_final_action", True)
         if compute_loss and self.training and not decode and not kwargs.get("decode_actions", False):
-            return None, loss_dict      # the training step: the action tuple is discarded (see _forward)
+            # Training step of the reference trainer (`_, losses = model(batch, compute_loss=True,
+            # compute_final_action=False)`, train_simple_policy.py:211): the action tuple is discarded, so
+            # the device->host argmax copy + per-sample scipy decode (simple_policy_ptv3.py:292-296) is
+            # skipped unless decode_actions=True is passed.  See INTEGRATION.md.
+            return None, loss_dict
         if mlp:
             pos = xt                    # compute_final_action has no effect on a continuous position
         elif decode:
-            best = act.get("best_disc_pos", "max")
-            if best == "ens1":
-                pos = ops.pos_decode_ens1(xt, pc, list(batch["npoints_in_batch"]), nb, act.pos_bin_size)
-            elif best == "max":
-                pos = ops.pos_decode_max(xt, pc, lvl.off, B, nb, act.pos_bin_size)
-            else:
-                raise ValueError(f"best_disc_pos must be 'max' or 'ens1', got {best!r}")
-            pos = pos.float()           # (simple_policy_ptv3.py:273)
+            pos = self.decode_disc_pos(act.get("best_disc_pos", "max"), xt, pc, batch["npoints_in_batch"], lvl, nb, act.pos_bin_size)
+            if not head.published:
+                pos = pos.float()       # (simple_policy_ptv3.py:273; the published head keeps the f64 position)
         else:
             pos = gt[..., :3]
-        from scipy.spatial.transform import Rotation as R
         if head.rot_pred_type == "euler_disc":
             # float64 quaternions: torch.cat promotes the whole action (simple_policy_ptv3.py:292-296)
-            rot_bins = torch.argmax(pred_rot, 1).cpu().numpy()
-            quat = np.stack([R.from_euler("xyz", x * head.euler_resolution - 180, degrees=True).as_quat() for x in rot_bins], 0)
-            quat = torch.from_numpy(quat).to(dev)
+            quat = self.decode_euler_disc(pred_rot, head.euler_resolution, dev)
         elif head.rot_pred_type == "euler":
             # simple_policy_ptv3.py:284-286 (RotationMatrixTransform.euler_to_quaternion: scipy 'xyz' in degrees), float32
+            from scipy.spatial.transform import Rotation as R
             eul = (pred_rot.detach() * 180).cpu().numpy()
             quat = torch.from_numpy(R.from_euler("xyz", eul, degrees=True).as_quat()).float().to(dev)
         else:
@@ -396,30 +370,19 @@ class SimplePolicyPTV3AdaNorm(SimplePolicyPTV3CA):
     `<site>.norm.*` + `<site>.modulation.1.*`, `txt_attn_fc` only for txt_reduce == 'attn', no CABlocks).
     fp32 activation storage; data parallel through parallel.GradReducer + SyncBatchNorm statistics like SimplePolicyPTV3CA."""
 
-    def __init__(self, config):
+    def _make_backbone(self, p3, act):
         from .adanorm import PointTransformerV3AdaNorm
 
-        BaseModel.__init__(self)
-        config = to_cfg(config)
-        self.config = config
-        p3 = {k: v for k, v in config.ptv3_config.items() if k in _PTV3_KEYS}
         p3.setdefault("pdnorm_only_decoder", False)  # (simple_policy_ptv3.py:165-167)
-        act = config.action_config
         p3["pdnorm_context_channels"] = act.context_channels
-        self.ptv3_model = PointTransformerV3AdaNorm(**p3)
+        backbone = PointTransformerV3AdaNorm(**p3)
         if act.txt_reduce not in ("mean", "attn"):
             raise NotImplementedError(f"txt_reduce={act.txt_reduce!r}: SimplePolicyPTV3AdaNorm builds 'mean' and 'attn'")
-        self.txt_fc = nn.Linear(act.txt_ft_size, act.context_channels)
+        return backbone
+
+    def _add_txt_reduce(self, act):
         if act.txt_reduce == "attn":
             self.txt_attn_fc = nn.Linear(act.txt_ft_size, 1)
-        if act.use_ee_pose:
-            self.pose_embedding = RobotPoseEmbedding(act.context_channels)
-        if act.use_step_id:
-            self.stepid_embedding = nn.Embedding(act.max_steps, act.context_channels)
-        self.act_proj_head = ActionHead(act.reduce, act.pos_pred_type, act.rot_pred_type,
-                                        config.ptv3_config.dec_channels[0], act.dim_actions, dropout=act.dropout,
-                                        voxel_size=act.voxel_size, pos_bins=act.pos_bins)
-        self.apply(self._init_weights)
 
     def prepare_ptv3_batch(self, batch):
         """simple_policy_ptv3.py:193-223: context = txt_fc(txt_embeds), reduced to one vector per cloud ('attn': softmax of

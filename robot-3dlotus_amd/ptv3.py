@@ -8,6 +8,8 @@ usual structure — while every forward/backward computation goes through robot_
 
 Only the configuration family of the published models is built (flash path, qk_norm, no RPE / PDNorm /
 cls_mode); other options raise NotImplementedError rather than silently computing something else.
+PointTransformerV3CA is also the skeleton of the adaptive-PDNorm backbone (adanorm.PointTransformerV3AdaNorm), which overrides its
+per-class steps; see the class docstring.
 """
 import os
 
@@ -158,7 +160,19 @@ class PointDict(dict):
     __getattr__ = dict.__getitem__
 
 
+class _Pass:
+    """What one forward pass hands to its per-stage steps: the levels, the dropout rates of this pass, the packed convolution
+    weights per Block, the context and the class's bank (ops.KvBank | adanorm.ModBank; `mods` = the ModBank's slices)."""
+    __slots__ = ("levels", "training", "p", "pa", "packs", "context", "bank", "mods")
+
+
 class PointTransformerV3CA(nn.Module):
+    """The constructor and `forward` are a fixed skeleton — option table, drop-path schedule, enc / dec module tree, forward
+    prologue, encoder / decoder walk — over a handful of steps a subclass overrides (adanorm.PointTransformerV3AdaNorm): the
+    PDNorm flag rule, the module factories, what runs at the top of a pass (stem and bank), pooling, unpooling and "the
+    block(s) at depth i of a stage"."""
+    block_cls = Block  # the type _blocks / _block_level index
+
     def __init__(self, in_channels=6, order=("z", "z-trans", "hilbert", "hilbert-trans"), stride=(2, 2, 2, 2),
                  enc_depths=(2, 2, 2, 6, 2), enc_channels=(32, 64, 128, 256, 512), enc_num_head=(2, 4, 8, 16, 32),
                  enc_patch_size=(1024,) * 5, dec_depths=(2, 2, 2, 2), dec_channels=(64, 64, 128, 256),
@@ -170,7 +184,8 @@ class PointTransformerV3CA(nn.Module):
                  pdnorm_conditions=("ScanNet", "S3DIS", "Structured3D"), pdnorm_only_decoder=False,
                  add_coords_in_attn=False, scaled_cosine_attn=False):
         super().__init__()
-        unsupported = dict(pdnorm_bn=pdnorm_bn, pdnorm_ln=pdnorm_ln, enable_rpe=enable_rpe, cls_mode=cls_mode,
+        pd = self._pdnorm_unsupported(pdnorm_bn, pdnorm_ln, pdnorm_decouple, pdnorm_adaptive, pdnorm_affine, pdnorm_only_decoder)
+        unsupported = dict(**pd, enable_rpe=enable_rpe, cls_mode=cls_mode,
                            scaled_cosine_attn=scaled_cosine_attn, not_flash=not enable_flash, not_qk_norm=not qk_norm,
                            not_pre_norm=not pre_norm, no_qkv_bias=not qkv_bias, qk_scale=qk_scale is not None,
                            add_coords=add_coords_in_attn not in (False, "none", None),
@@ -182,6 +197,7 @@ class PointTransformerV3CA(nn.Module):
             raise NotImplementedError(f"lotus-hip builds the published 3D-LOTUS configuration family only; unsupported: {bad}")
         if len(set(enc_patch_size) | set(dec_patch_size)) != 1:
             raise NotImplementedError("all patch sizes must be equal")
+        self.context_channels = int(self._context_width(ctx_channels, pdnorm_context_channels))
         self.num_stages = len(enc_depths)
         self.order = list(order)
         self.shuffle_orders = shuffle_orders
@@ -199,50 +215,79 @@ class PointTransformerV3CA(nn.Module):
         self.dec_drop_path = [list(reversed(dd[sum(self.dec_depths[:s]):sum(self.dec_depths[:s + 1])]))
                               for s in range(self.num_stages - 1)]
 
-        self.embedding = _Embedding(in_channels, enc_channels[0])
+        self.embedding = self._make_embedding(in_channels, enc_channels[0])
         self.enc = nn.Sequential()
         for s in range(self.num_stages):
             enc = nn.Sequential()
             if s > 0:
-                enc.add_module("down", _Down(enc_channels[s - 1], enc_channels[s]))
-            for i in range(self.enc_depths[s]):  # model_ca.py:270-310: Block i, then CABlock i
-                enc.add_module(f"block{i}", Block(enc_channels[s], enc_num_head[s], mlp_ratio))
-                enc.add_module(f"ca_block{i}", CABlock(enc_channels[s], enc_num_head[s], ctx_channels, mlp_ratio))
+                enc.add_module("down", self._make_down(enc_channels[s - 1], enc_channels[s]))
+            for i in range(self.enc_depths[s]):  # model_ca.py:270-310
+                self._add_depth(enc, i, enc_channels[s], enc_num_head[s], mlp_ratio)
             self.enc.add_module(f"enc{s}", enc)
         self.dec = nn.Sequential()
         dc = self.dec_channels
         for s in reversed(range(self.num_stages - 1)):
             dec = nn.Sequential()
-            dec.add_module("up", _Up(dc[s + 1], enc_channels[s], dc[s]))
+            dec.add_module("up", self._make_up(dc[s + 1], enc_channels[s], dc[s]))
             for i in range(self.dec_depths[s]):  # model_ca.py:340-380
-                dec.add_module(f"block{i}", Block(dc[s], dec_num_head[s], mlp_ratio))
-                dec.add_module(f"ca_block{i}", CABlock(dc[s], dec_num_head[s], ctx_channels, mlp_ratio))
+                self._add_depth(dec, i, dc[s], dec_num_head[s], mlp_ratio)
             self.dec.add_module(f"dec{s}", dec)
-        self._blocks = [m for m in self.modules() if isinstance(m, Block)]
+        self._blocks = [m for m in self.modules() if isinstance(m, self.block_cls)]
         # level every Block works at (encoder stage s -> level s; the decoder modules are stored in execution order)
         self._block_level = {}
         for s in range(self.num_stages):
             for m in self.enc[s].children():
-                if isinstance(m, Block):
+                if isinstance(m, self.block_cls):
                     self._block_level[id(m)] = s
         for i, s in enumerate(reversed(range(self.num_stages - 1))):
             for m in self.dec[i].children():
-                if isinstance(m, Block):
+                if isinstance(m, self.block_cls):
                     self._block_level[id(m)] = s
-        # every CABlock in execution order (module order = encoder stages, then decoder stages as they run): their kv
-        # projections of the shared context are evaluated as one product at the top of forward (ops.KvAllFn)
-        self._cablocks = [m for m in self.modules() if isinstance(m, CABlock)]
-        self._cab_index = {id(m): i for i, m in enumerate(self._cablocks)}
-        self._pair_params = {}  # (Block, CABlock) -> their 38 parameters in ops._PAIR_PARAM_SLOTS order (module walks cost host time)
-        self.kv_group = os.environ.get("LOTUS_KV_GROUP", "1") != "0"
+        self._index_sites()
         self._step = None  # dropout stream position; taken from stem.norm.num_batches_tracked on first use (see _seeds)
         self._seed_base = None
         self.order_perms = None  # inject a list of permutations to override the RNG draw (tests)
         self._pending, self._deferred, self._fe_stream = None, None, None  # prefetch() state
-        self._nbt = None
         self._sync_bn_checked = False
+        self._drop_param_caches()
         self.register_load_state_dict_post_hook(lambda m, _keys: setattr(m, "_step", None))
 
+    # -- per class: construction ------------------------------------------------------------
+    @staticmethod
+    def _pdnorm_unsupported(pdnorm_bn, pdnorm_ln, pdnorm_decouple, pdnorm_adaptive, pdnorm_affine, pdnorm_only_decoder):
+        """The PDNorm flag rule -> leading entries of the `unsupported` table (or raises): the CA backbone has no PDNorm."""
+        return dict(pdnorm_bn=pdnorm_bn, pdnorm_ln=pdnorm_ln)
+
+    @staticmethod
+    def _context_width(ctx_channels, pdnorm_context_channels):
+        return ctx_channels
+
+    def _make_embedding(self, cin, cout):
+        return _Embedding(cin, cout)
+
+    def _make_down(self, cin, cout):
+        return _Down(cin, cout)
+
+    def _make_up(self, cin, cskip, cout):
+        return _Up(cin, cskip, cout)
+
+    def _add_depth(self, stage, i, c, h, mlp_ratio):
+        """Depth index i of a stage (model_ca.py:270-310): Block i, then CABlock i."""
+        stage.add_module(f"block{i}", Block(c, h, mlp_ratio))
+        stage.add_module(f"ca_block{i}", CABlock(c, h, self.context_channels, mlp_ratio))
+
+    def _index_sites(self):
+        # every CABlock in execution order (module order = encoder stages, then decoder stages as they run): their kv
+        # projections of the shared context are evaluated as one product at the top of forward (ops.KvAllFn)
+        self._cablocks = [m for m in self.modules() if isinstance(m, CABlock)]
+        self._cab_index = {id(m): i for i, m in enumerate(self._cablocks)}
+        self.kv_group = os.environ.get("LOTUS_KV_GROUP", "1") != "0"
+
+    def _drop_param_caches(self):
+        self._pair_params = {}  # (Block, CABlock) -> their 38 parameters in ops._PAIR_PARAM_SLOTS order (module walks cost host time)
+        self._nbt = None
+
+    # -- shared state ---------------------------------------------------------------------------
     def _bn_counters(self):
         """num_batches_tracked of every norm layer — BatchNorm1d, or SyncBatchNorm after convert_sync_batchnorm (not a
         BatchNorm1d subclass)."""
@@ -273,34 +318,8 @@ class PointTransformerV3CA(nn.Module):
             from . import parallel
             parallel.enable_sync_batchnorm()
 
-    def _pair(self, blk, cab, x, xs, lvl_o, lvl, p, si, pa, wt, bank, mlp_ratio_hd=None):
-        """Block + CABlock as one autograd node (ops.PairFn): same seeds, same launches, same results as blk.run(...) followed by
-        cab.run(...), a fifth of the host work."""
-        key = (id(blk), id(cab))
-        ps = self._pair_params.get(key)
-        if ps is None:
-            c0, c1, c2 = blk.cpe[0], blk.cpe[1], blk.cpe[2]
-            a, n1, n2, m = blk.attn, blk.norm1[0], blk.norm2[0], blk.mlp[0]
-            ca, cn1, cn2, cm = cab.attn, cab.norm1[0], cab.norm2[0], cab.mlp[0]
-            ps = (c0.weight, c0.bias, c1.weight, c1.bias, c2.weight, c2.bias,
-                  n1.weight, n1.bias, a.qkv.weight, a.qkv.bias, a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias,
-                  a.proj.weight, a.proj.bias, n2.weight, n2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                  cn1.weight, cn1.bias, ca.q.weight, ca.q.bias, ca.q_norm.weight, ca.q_norm.bias, ca.k_norm.weight, ca.k_norm.bias,
-                  ca.proj.weight, ca.proj.bias, cn2.weight, cn2.bias, cm.fc1.weight, cm.fc1.bias, cm.fc2.weight, cm.fc2.bias)
-            self._pair_params[key] = ps
-        sc = ops.mix_seed(si, 8)  # the CABlock's seed (cab.run(..., ops.mix_seed(si, 8), ...))
-        meta = (lvl_o, lvl, blk.num_heads, ps[18].shape[0], p, pa, si, ops.mix_seed(si, 2), sc, ops.mix_seed(sc, 2), bank,
-                self._cab_index[id(cab)])
-        return ops.PairFn.apply(x, xs, bank.slice(self._cab_index[id(cab)]), wt, *ps, meta)
-
-    def _pair_ok(self, blk, bank, dpath):
-        c = blk.cpe[0].weight.shape[0]
-        return (bank is not None and dpath == 0.0 and self._pair_on and c % 64 == 0 and (c == 64 or c % 128 == 0)
-                and c // blk.num_heads % 4 == 0)
-
     def _apply(self, fn, *a, **kw):  # (parameters may be replaced: drop the cached tuples)
-        self._pair_params = {}
-        self._nbt = None
+        self._drop_param_caches()
         return super()._apply(fn, *a, **kw)
 
     def _pack(self, feat, lvl):
@@ -365,12 +384,14 @@ class PointTransformerV3CA(nn.Module):
         perms = self.order_perms if self.order_perms is not None else draw_order_perms(self.num_stages, self.shuffle_orders)
         self._pending = self.frontend.launch(src, counts, perms, stream=self._fe_stream, wait_current=wait_current)
 
+    # -- forward: prologue and walk (shared), steps (per class) -----------------------------------
     def forward(self, data_dict, return_dec_layers=False):
         """data_dict keys as in the reference: coord / feat / offset / context / context_offset
         (+ grid_size).  Extra host-side hints `counts` / `context_counts` (python lists) avoid two
         device->host copies.  Returns the list [enc_last, dec..] of {feat, coord, offset} when
         return_dec_layers, else the last dict (model_ca.py:383-412)."""
         feat, src, counts, ctx_counts, context = self._front_inputs(data_dict)
+        self._check_inputs(feat, counts, context)  # (before the prefetched tables are consumed)
         pend, self._pending = self._pending, None
         if pend is not None and pend["pc_fts"] is src and pend["counts"] == list(counts):
             levels = self.frontend.finish(pend, ctx_counts, need_coord=True)  # prefetched: no pipeline drain
@@ -384,79 +405,124 @@ class PointTransformerV3CA(nn.Module):
         training = self.training
         if not self._sync_bn_checked:
             self._check_sync_bn()
-        p = self.proj_drop if training else 0.0
-        pa = self.attn_drop if training else 0.0
+        fw = _Pass()
+        fw.levels, fw.training, fw.context = levels, training, context
+        fw.p = self.proj_drop if training else 0.0
+        fw.pa = self.attn_drop if training else 0.0
         base = self._seeds() if training else 0
         self.last_seed = base  # the policy head derives its dropout seeds from the same (rank, step) stream
         if training:  # num_batches_tracked += 1 for every norm layer (BatchNorm1d or SyncBatchNorm), one fused launch
             nbt = self._bn_counters()
             if nbt:
                 torch._foreach_add_(nbt, 1)
-        site = 0
 
-        st = self.embedding.stem
         blocks = self._blocks  # every Block of the model, in module order (cached: a tree walk per forward costs 0.4 ms)
         # (convolutions on the tap-grouped path read the module's weight tensor itself: 134 of the 143 MB of packing in v1)
         need = [b for b in blocks if not ops.conv_tap_active(levels[self._block_level[id(b)]], b.cpe[0].weight.shape[0])]
-        packs = dict(zip(need, ops.prepack_conv_weights([b.cpe[0].weight for b in need])))
+        fw.packs = packs = dict(zip(need, ops.prepack_conv_weights([b.cpe[0].weight for b in need])))
         if len(need) < len(blocks):
             none = ops.no_pack(feat.device)
             for b in blocks:
                 packs.setdefault(b, none)
-        n_ord = len(self.order)
-        # optional effective stem weight (a differentiable function of st.conv.weight) for callers whose input
-        # features are a linear code of something smaller, e.g. the motion planner's label embedding
-        x = ops.StemFn.apply(feat, data_dict.get("stem_weight", st.conv.weight), st.norm.weight, st.norm.bias, st.norm.running_mean,
-                             st.norm.running_var, levels[0], training)
-        ops.sync_side_stream()  # the packed convolution weights (they overlapped the stem)
-        bank, cidx = None, self._cab_index
-        self._pair_on = False  # decided per stage below: ops.pair_enabled(points of the stage's level)
-        if self.kv_group and context is not None and len(self._cablocks) > 1:
-            bank = ops.KvBank()
-            wb = []
-            for c in self._cablocks:
-                wb += [c.attn.kv.weight, c.attn.kv.bias]
-            ops.KvAllFn.apply(context, bank, *wb)
+        x = self._begin(fw, data_dict, feat)
+
+        site = 0
         skips = []
         for s in range(self.num_stages):
             enc, lvl = self.enc[s], levels[s]
             site += 1
             seed = ops.mix_seed(base, site)
-            self._pair_on = ops.pair_enabled(lvl.n, levels[0].n)
+            self._enter_stage(fw, lvl)
             if s > 0:
-                d, bn = enc.down, enc.down.norm[0]
-                x = ops.PoolFn.apply(x, d.proj.weight, d.proj.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                     lvl, training)
-            for i in range(self.enc_depths[s]):
-                blk, cab = getattr(enc, f"block{i}"), getattr(enc, f"ca_block{i}")
-                si = seed if i == 0 else ops.mix_seed(seed, 16 + i)
-                dpath = self.enc_drop_path[s][i] if training else 0.0
-                if self._pair_ok(blk, bank, dpath):
-                    x = self._pair(blk, cab, x, x, lvl.for_order(i % n_ord), lvl, p, si, pa, packs[blk], bank)
-                    continue
-                x, hand = blk.run(x, x, lvl.for_order(i % n_ord), p, si, pa, packs[blk], dpath)
-                x = cab.run(x, context, lvl, p, ops.mix_seed(si, 8), pa, hand, bank, cidx[id(cab)])
+                x = self._pool(fw, enc.down, x, lvl)
+            x = self._run_stage(fw, enc, self.enc_depths[s], self.enc_drop_path[s], x, x, lvl, seed)
             skips.append(x)
         outs = [self._pack(x, levels[-1])]
         for i, s in enumerate(reversed(range(self.num_stages - 1))):
             dec, lvl, child = self.dec[i], levels[s], levels[s + 1]
             site += 1
             seed = ops.mix_seed(base, site)
-            self._pair_on = ops.pair_enabled(lvl.n, levels[0].n)
-            u, us = dec.up.proj, dec.up.proj_skip
-            x, skip = ops.UnpoolFn.apply(x, skips[s], u[0].weight, u[0].bias, u[1].weight, u[1].bias, u[1].running_mean,
-                                         u[1].running_var, us[0].weight, us[0].bias, us[1].weight, us[1].bias,
-                                         us[1].running_mean, us[1].running_var, child, training)
-            for j in range(self.dec_depths[s]):
-                blk, cab = getattr(dec, f"block{j}"), getattr(dec, f"ca_block{j}")
-                si = seed if j == 0 else ops.mix_seed(seed, 16 + j)
-                # only the first Block of a decoder stage sees the stale skip branch in its CPE convolution (Trap 3):
-                # every Block / CABlock ends with sparse_conv_feat.replace_feature(feat) (model.py:678, model_ca.py:151)
-                dpath = self.dec_drop_path[s][j] if training else 0.0
-                if self._pair_ok(blk, bank, dpath):
-                    x = self._pair(blk, cab, x, skip if j == 0 else x, lvl.for_order(j % n_ord), lvl, p, si, pa, packs[blk], bank)
-                    continue
-                x, hand = blk.run(x, skip if j == 0 else x, lvl.for_order(j % n_ord), p, si, pa, packs[blk], dpath)
-                x = cab.run(x, context, lvl, p, ops.mix_seed(si, 8), pa, hand, bank, cidx[id(cab)])
+            self._enter_stage(fw, lvl)
+            x, skip = self._unpool(fw, dec.up, x, skips[s], child, lvl)
+            x = self._run_stage(fw, dec, self.dec_depths[s], self.dec_drop_path[s], x, skip, lvl, seed)
             outs.append(self._pack(x, lvl))
         return outs if return_dec_layers else outs[-1]
+
+    def _run_stage(self, fw, stage, depth, rates, x, xs0, lvl, seed):
+        """The `depth` block positions of one stage.  xs0 = what the FIRST Block's CPE convolves: x itself in the encoder, the
+        stale skip branch in the decoder — only the first Block of a decoder stage sees it (Trap 3): every Block / CABlock ends
+        with sparse_conv_feat.replace_feature(feat) (model.py:678, model_ca.py:151)."""
+        n_ord = len(self.order)
+        for i in range(depth):
+            si = seed if i == 0 else ops.mix_seed(seed, 16 + i)
+            dpath = rates[i] if fw.training else 0.0
+            x = self._run_depth(fw, stage, i, x, xs0 if i == 0 else x, lvl.for_order(i % n_ord), lvl, si, dpath)
+        return x
+
+    # -- per class: the steps of a pass ----------------------------------------------------------
+    def _check_inputs(self, feat, counts, context):
+        pass
+
+    def _begin(self, fw, data_dict, feat):
+        """Top of a pass -> stem output: stem, join of the packed convolution weights, then the kv bank of every CABlock."""
+        st = self.embedding.stem
+        # optional effective stem weight (a differentiable function of st.conv.weight) for callers whose input
+        # features are a linear code of something smaller, e.g. the motion planner's label embedding
+        x = ops.StemFn.apply(feat, data_dict.get("stem_weight", st.conv.weight), st.norm.weight, st.norm.bias, st.norm.running_mean,
+                             st.norm.running_var, fw.levels[0], fw.training)
+        ops.sync_side_stream()  # the packed convolution weights (they overlapped the stem)
+        fw.bank = None
+        self._pair_on = False  # decided per stage (_enter_stage): ops.pair_enabled(points of the stage's level)
+        if self.kv_group and fw.context is not None and len(self._cablocks) > 1:
+            fw.bank = ops.KvBank()
+            wb = []
+            for c in self._cablocks:
+                wb += [c.attn.kv.weight, c.attn.kv.bias]
+            ops.KvAllFn.apply(fw.context, fw.bank, *wb)
+        return x
+
+    def _enter_stage(self, fw, lvl):
+        self._pair_on = ops.pair_enabled(lvl.n, fw.levels[0].n)
+
+    def _pool(self, fw, d, x, lvl):
+        bn = d.norm[0]
+        return ops.PoolFn.apply(x, d.proj.weight, d.proj.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, lvl, fw.training)
+
+    def _unpool(self, fw, up, x, skip, child, lvl):
+        u, us = up.proj, up.proj_skip
+        return ops.UnpoolFn.apply(x, skip, u[0].weight, u[0].bias, u[1].weight, u[1].bias, u[1].running_mean,
+                                  u[1].running_var, us[0].weight, us[0].bias, us[1].weight, us[1].bias,
+                                  us[1].running_mean, us[1].running_var, child, fw.training)
+
+    def _run_depth(self, fw, stage, i, x, xs, lvl_o, lvl, si, dpath):
+        """Block i + CABlock i: one autograd node (_pair) where that is built, else blk.run then cab.run."""
+        blk, cab = getattr(stage, f"block{i}"), getattr(stage, f"ca_block{i}")
+        if self._pair_ok(blk, fw.bank, dpath):
+            return self._pair(blk, cab, x, xs, lvl_o, lvl, fw.p, si, fw.pa, fw.packs[blk], fw.bank)
+        x, hand = blk.run(x, xs, lvl_o, fw.p, si, fw.pa, fw.packs[blk], dpath)
+        return cab.run(x, fw.context, lvl, fw.p, ops.mix_seed(si, 8), fw.pa, hand, fw.bank, self._cab_index[id(cab)])
+
+    def _pair(self, blk, cab, x, xs, lvl_o, lvl, p, si, pa, wt, bank, mlp_ratio_hd=None):
+        """Block + CABlock as one autograd node (ops.PairFn): same seeds, same launches, same results as blk.run(...) followed by
+        cab.run(...), a fifth of the host work."""
+        key = (id(blk), id(cab))
+        ps = self._pair_params.get(key)
+        if ps is None:
+            c0, c1, c2 = blk.cpe[0], blk.cpe[1], blk.cpe[2]
+            a, n1, n2, m = blk.attn, blk.norm1[0], blk.norm2[0], blk.mlp[0]
+            ca, cn1, cn2, cm = cab.attn, cab.norm1[0], cab.norm2[0], cab.mlp[0]
+            ps = (c0.weight, c0.bias, c1.weight, c1.bias, c2.weight, c2.bias,
+                  n1.weight, n1.bias, a.qkv.weight, a.qkv.bias, a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias,
+                  a.proj.weight, a.proj.bias, n2.weight, n2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
+                  cn1.weight, cn1.bias, ca.q.weight, ca.q.bias, ca.q_norm.weight, ca.q_norm.bias, ca.k_norm.weight, ca.k_norm.bias,
+                  ca.proj.weight, ca.proj.bias, cn2.weight, cn2.bias, cm.fc1.weight, cm.fc1.bias, cm.fc2.weight, cm.fc2.bias)
+            self._pair_params[key] = ps
+        sc = ops.mix_seed(si, 8)  # the CABlock's seed (cab.run(..., ops.mix_seed(si, 8), ...))
+        meta = (lvl_o, lvl, blk.num_heads, ps[18].shape[0], p, pa, si, ops.mix_seed(si, 2), sc, ops.mix_seed(sc, 2), bank,
+                self._cab_index[id(cab)])
+        return ops.PairFn.apply(x, xs, bank.slice(self._cab_index[id(cab)]), wt, *ps, meta)
+
+    def _pair_ok(self, blk, bank, dpath):
+        c = blk.cpe[0].weight.shape[0]
+        return (bank is not None and dpath == 0.0 and self._pair_on and c % 64 == 0 and (c == 64 or c % 128 == 0)
+                and c // blk.num_heads % 4 == 0)
