@@ -21,6 +21,9 @@ SYNC_WAIT = None  # set to [0.0] to accumulate the host time FrontEnd.finish() w
 FINISH_ON_SIDE = True  # exact-size tables of a prefetched batch are built on the front-end stream (+0.6 % with fresh batches)
 
 ORDERS = ("z", "z-trans", "hilbert", "hilbert-trans")
+# longest context (instruction tokens of one cloud) the cross attention is built for: the tile kernels of csrc/attention.hip
+# keep one 128-row key image in LDS and index it by tid < 128 (the reference hands over at most 77 CLIP tokens + 1)
+MAX_CTX = 128
 
 
 class _Arena:
@@ -195,7 +198,12 @@ class FrontEnd:
     def finish(self, pend, ctx_counts, need_coord=False):
         """Second half of build(): wait for the counts (the one host synchronisation of the front-end; free when
         launch() ran ahead on a side stream), then build the exactly sized neighbour / patch / tile tables on the
-        current stream."""
+        current stream.  A context longer than MAX_CTX tokens raises ValueError (DESIGN.md sections 7 and 8: what is not built raises
+        by name); contexts of length 0 are passed through as they are — the reference's behaviour there is not pinned."""
+        longest = max(ctx_counts) if len(ctx_counts) else 0
+        if longest > MAX_CTX:
+            raise ValueError(f"context of {int(longest)} tokens: the cross attention is built for at most {MAX_CTX} keys per cloud "
+                             f"(csrc/attention.hip)")
         pc_fts, counts, perms, raw = pend["pc_fts"], pend["counts"], pend["perms"], pend["raw"]
         dev = pc_fts.device
         N, B, Lv = int(pc_fts.shape[0]), len(counts), self.n_levels
