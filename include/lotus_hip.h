@@ -403,8 +403,8 @@ int lotus_cpe_bwd(const lotus_act_t* dy, const lotus_act_t* xs, const float* cw,
 /* One (Block, CABlock) pair of a stage per call (round 4): cpe -> self-attention -> mlp -> cross-attention (kv from the
  * shared slab) -> mlp, model_ca.py:270-310, forward or backward, with the hand-overs of the pre-masked gradients wired
  * inside — exactly the launches of the five composite calls above, bit-identical results, one host transition.  Arguments
- * travel in three HOST arrays: P = device pointers (enum PairPtr in csrc/blocks.cpp, lotus_pair_nptr() entries), I =
- * integers incl. seeds, strides and byte sizes (enum PairInt, lotus_pair_nint()), F = {drop_p, attn_p, scale}.
+ * travel in three HOST arrays: P = device pointers (lotus_pair_nptr() entries, named by lotus_pair_ptr_names()), I =
+ * integers incl. seeds, strides and byte sizes (lotus_pair_nint(), lotus_pair_int_names()), F = {drop_p, attn_p, scale}.
  *   acts  [x1 | x2 | x3 | x4]           (outputs of the first four sub-blocks, kept for backward)
  *   saved / grads / tmp = the five composites' buffers back to back (cpe, self, mlp, cross_kv, mlp; tmp + 4 M*C) */
 size_t lotus_pair_acts_floats(int M, int C);
@@ -416,8 +416,19 @@ size_t lotus_pair_ws_side_bytes(int M, int C, int Hd);
 size_t lotus_pair_ws_conv_bytes(int M, int C);
 int lotus_pair_nptr(void);
 int lotus_pair_nint(void);
+/* The names of the P / I entries in index order, separated by blanks ("X XS KV Y ..." / "M C H HD ..."): the list in
+ * csrc/blocks.cpp that the enums are generated from.  A caller looks its indices up by name (ops._pair_tables). */
+const char* lotus_pair_ptr_names(void);
+const char* lotus_pair_int_names(void);
 int lotus_pair_fwd(const void* const* P, const long long* I, const double* F);
 int lotus_pair_bwd(const void* const* P, const long long* I, const double* F);
+/* Where each parameter gradient lies in the `grads` slab of a composite, from the layout definition in csrc/blocks.cpp that
+ * the entry points themselves use: fills off[i] / len[i] (floats) for the first `cap` fields in slab order — the order
+ * of the `grads [...]` lines above, a weight and its bias as two fields — and returns the number of fields (ffn 6,
+ * selfattn 10, crossattn 12, crossattn_kv 10, cpe 6; the pair 38: cpe, selfattn, ffn, crossattn_kv, ffn of model_ca.py:270-310
+ * one after the other).  kind: 0 ffn, 1 selfattn, 2 crossattn, 3 crossattn_kv, 4 cpe, 5 pair; dimensions that a kind does
+ * not have are ignored.  Host only, nothing is launched.  Gradients are fp32 in both builds: the twin returns the same. */
+int lotus_composite_grads_layout(int kind, int C, int H, int Hd, int Cc, long long* off, long long* len, int cap);
 /* out[e] = sum_z part[z * stride + e] in fixed order (e.g. the key-side partial slots of the cross-attention backward) */
 int lotus_sum_slabs(const lotus_act_t* part, lotus_act_t* out, long n, long stride, int nz, void* stream);
 /* out[r][c] (row stride out_ld) = sum_z part[z * stride + r * cols + c]: the same sum written into a column slice of a wider slab */

@@ -525,6 +525,14 @@ class Handoff:
         dz, self.dz = self.dz, None
         return dz if (dz is not None and self.ptr == dy.data_ptr() and dz.shape == dy.shape) else None
 
+    @staticmethod
+    def offer(hand, dx):         # B.backward -> (dz_out, p, seed) for the LayerNorm backward that writes dx
+        if hand is None or hand.drop is None:
+            return None, 0.0, 0
+        dz = torch.empty_like(dx)
+        hand.ptr, hand.dz = dx.data_ptr(), dz
+        return (dz,) + hand.drop
+
 
 def _masked(dy, p, seed, hand):
     """dz = dropout mask * dy for a backward pass: from the hand-over if the producer of dy left it, else a launch."""
@@ -540,11 +548,7 @@ def ln_bwd(dy, x, mean, rstd, g, add=None, hand=None):
     dx = torch.empty_like(x)
     dg = torch.empty(C, dtype=torch.float32, device=x.device)
     db = torch.empty(C, dtype=torch.float32, device=x.device)
-    dz, dp, dseed = None, 0.0, 0
-    if hand is not None and hand.drop is not None:
-        dp, dseed = hand.drop
-        dz = torch.empty_like(x)
-        hand.ptr, hand.dz = dx.data_ptr(), dz
+    dz, dp, dseed = Handoff.offer(hand, dx)
     nbytes = query("lotus_layernorm_bwd_workspace", M, C)
     if _side() is None:
         ws = _ws(nbytes, x.device)
@@ -978,46 +982,90 @@ def set_composites(on):
     _COMPOSITE = bool(on)
 
 
+def _queries(prefix, dims, spec):
+    return dims.split(), [(prefix + q.split(":")[0], q.split(":")[1].split(",")) for q in spec.split()]
+
+
+# kind -> (names of its dims, its size queries with their arguments in the order _sizes returns them)
+_SIZE_QUERIES = {
+    "ffn": _queries("lotus_ffn_", "M C Hd", "saved_floats:M,C,Hd grads_floats:C,Hd tmp_floats:M,C,Hd ws_main_bytes:M,C,Hd ws_side_bytes:M,C,Hd"),
+    "self": _queries("lotus_selfattn_", "M C H npad nblocks n_extra", "saved_floats:M,C,H,npad grads_floats:C,H tmp_floats:M,C,n_extra "
+                     "ws_main_bytes:M,C,H,nblocks ws_side_bytes:M,C"),
+    "cross": _queries("lotus_crossattn_", "M C H L Cc nblocks G", "saved_floats:M,C,H,L grads_floats:C,H,Cc tmp_floats:M,C,L,G "
+                      "ws_main_bytes:M,C,H,L,Cc,nblocks ws_side_bytes:M,C,L,Cc"),
+    "crosskv": _queries("lotus_crossattn_kv_", "M C H L nblocks G", "saved_floats:M,C,H grads_floats:C,H tmp_floats:M,C,L,G "
+                        "ws_main_bytes:M,C,H,nblocks ws_side_bytes:M,C"),
+    "pair": _queries("lotus_pair_", "M C H Hd npad nst n_extra L nca G", "acts_floats:M,C saved_floats:M,C,H,Hd,npad grads_floats:C,H,Hd "
+                     "tmp_floats:M,C,Hd,n_extra,L,G ws_main_bytes:M,C,H,Hd,nst,nca ws_side_bytes:M,C,Hd ws_conv_bytes:M,C"),
+    "cpe": _queries("lotus_cpe_", "n C", "saved_floats:n,C grads_floats:C tmp_floats:n,C ws_main_bytes:n,C ws_side_bytes:n,C ws_conv_bytes:n,C"),
+}
+
+
 def _sizes(kind, *dims):
     key = (kind, _capi.BF16) + dims
     v = _SIZE_CACHE.get(key)
     if v is None:
-        if kind == "ffn":
-            M, C, Hd = dims
-            v = (query("lotus_ffn_saved_floats", M, C, Hd), query("lotus_ffn_grads_floats", C, Hd),
-                 query("lotus_ffn_tmp_floats", M, C, Hd), query("lotus_ffn_ws_main_bytes", M, C, Hd),
-                 query("lotus_ffn_ws_side_bytes", M, C, Hd))
-        elif kind == "self":
-            M, C, H, npad, nblocks, n_extra = dims
-            v = (query("lotus_selfattn_saved_floats", M, C, H, npad), query("lotus_selfattn_grads_floats", C, H),
-                 query("lotus_selfattn_tmp_floats", M, C, n_extra), query("lotus_selfattn_ws_main_bytes", M, C, H, nblocks),
-                 query("lotus_selfattn_ws_side_bytes", M, C))
-        elif kind == "cross":
-            M, C, H, L, Cc, nblocks, G = dims
-            v = (query("lotus_crossattn_saved_floats", M, C, H, L), query("lotus_crossattn_grads_floats", C, H, Cc),
-                 query("lotus_crossattn_tmp_floats", M, C, L, G), query("lotus_crossattn_ws_main_bytes", M, C, H, L, Cc, nblocks),
-                 query("lotus_crossattn_ws_side_bytes", M, C, L, Cc))
-        elif kind == "crosskv":
-            M, C, H, L, nblocks, G = dims
-            v = (query("lotus_crossattn_kv_saved_floats", M, C, H), query("lotus_crossattn_kv_grads_floats", C, H),
-                 query("lotus_crossattn_kv_tmp_floats", M, C, L, G), query("lotus_crossattn_kv_ws_main_bytes", M, C, H, nblocks),
-                 query("lotus_crossattn_kv_ws_side_bytes", M, C))
-        elif kind == "pair":
-            M, C, H, Hd, npad, nst, n_extra, L, nca, G = dims
-            v = (query("lotus_pair_acts_floats", M, C), query("lotus_pair_saved_floats", M, C, H, Hd, npad),
-                 query("lotus_pair_grads_floats", C, H, Hd), query("lotus_pair_tmp_floats", M, C, Hd, n_extra, L, G),
-                 query("lotus_pair_ws_main_bytes", M, C, H, Hd, nst, nca), query("lotus_pair_ws_side_bytes", M, C, Hd),
-                 query("lotus_pair_ws_conv_bytes", M, C))
-        elif kind == "cpe":
-            n, C = dims
-            v = (query("lotus_cpe_saved_floats", n, C), query("lotus_cpe_grads_floats", C), query("lotus_cpe_tmp_floats", n, C),
-                 query("lotus_cpe_ws_main_bytes", n, C), query("lotus_cpe_ws_side_bytes", n, C), query("lotus_cpe_ws_conv_bytes", n, C))
-        _SIZE_CACHE[key] = v
+        names, queries = _SIZE_QUERIES[kind]
+        d = dict(zip(names, dims))
+        assert len(d) == len(dims) == len(names), (kind, dims)
+        v = _SIZE_CACHE[key] = tuple(query(q, *[d[a] for a in args]) for q, args in queries)
     return v
 
 
-def _al4(n):
-    return (n + 3) & ~3
+# Where each parameter gradient lies in the `grads` slab of a composite is defined in csrc/blocks.cpp, next to the code that
+# writes it, and asked for here (lotus_composite_grads_layout: (offset, length) per field in slab order).  What Python adds per
+# kind is the order in which the autograd node returns them and the 2-D shapes of the weights: (field, shape or None) below.
+_GRAD_KINDS = {"ffn": 0, "self": 1, "cross": 2, "crosskv": 3, "cpe": 4, "pair": 5}
+
+
+def _grad_returns(kind, C, Hd, Cc, cshape):
+    cpe = ((4, cshape), 5, (2, (C, C)), 3, 0, 1)   # returned as dcw, dcb, dlw, dlb, dg, db
+    att = (0, 1, (2, (3 * C, C)), 3, 4, 5, 6, 7, (8, (C, C)), 9)
+    ffn = (0, 1, (2, (Hd, C)), 3, (4, (C, Hd)), 5)
+    ca = (0, 1, (2, (C, C)), 3, 4, 5, 6, 7, (8, (C, C)), 9)
+    cross = (0, 1, (2, (C, C)), 3, (4, (2 * C, Cc)), 5, 6, 7, 8, 9, (10, (C, C)), 11)
+    subs = {"ffn": (ffn,), "self": (att,), "cross": (cross,), "crosskv": (ca,), "cpe": (cpe,), "pair": (cpe, att, ffn, ca, ffn)}[kind]
+    out, first = [], 0
+    for sub in subs:   # (the pair: its five sub-blocks one after the other, i.e. the 38 parameters in _PAIR_PARAM_SLOTS order)
+        out += [(first + f[0], f[1]) if isinstance(f, tuple) else (first + f, None) for f in sub]
+        first += len(sub)
+    return out
+
+
+def _grad_views(grads, kind, C, H=1, Hd=0, Cc=0, cshape=None):
+    """The parameter gradients of a composite backward as views of its `grads` slab, in the node's return order.  The plan
+    (split sizes, then chunk index and shape per returned tensor) is computed once per (kind, dims)."""
+    key = ("grads", kind, C, H, Hd, Cc, cshape)
+    plan = _SIZE_CACHE.get(key)
+    if plan is None:
+        import numpy as np
+        off, length = np.zeros(64, dtype=np.int64), np.zeros(64, dtype=np.int64)
+        n = query("lotus_composite_grads_layout", _GRAD_KINDS[kind], C, H, Hd, Cc, off.ctypes.data, length.ctypes.data, 64)
+        returns = _grad_returns(kind, C, Hd, Cc, cshape)
+        if not 0 < n <= 64 or sorted(f for f, _ in returns) != list(range(n)):
+            raise _capi.LotusError(f"lotus_composite_grads_layout({kind}) reports {n} fields, ops returns {len(returns)}")
+        sizes, chunk, end = [], {}, 0
+        for f in range(n):   # split sizes: the fields, and the padding between them as chunks of their own
+            if off[f] > end:
+                sizes.append(int(off[f]) - end)
+            chunk[f] = len(sizes)
+            sizes.append(int(length[f]))
+            end = int(off[f] + length[f])
+        if grads.numel() > end:
+            sizes.append(grads.numel() - end)
+        plan = _SIZE_CACHE[key] = (sizes, tuple((chunk[f], shape) for f, shape in returns))
+    parts = grads.split(plan[0])
+    return tuple([parts[i] if shape is None else parts[i].view(shape) for i, shape in plan[1]])
+
+
+def _bwd_buffers(n_grads, n_tmp, ws_main, ws_side, dev, reads, rows):
+    """What every composite backward allocates -> (grads, tmp, main workspace, side stream pointer or 0, its workspace, that
+    workspace's bytes, its counters); `reads`: what the side stream reads besides tmp (see _side_ctx)."""
+    grads = _grad_slab(n_grads, dev)
+    tmp = torch.empty(n_tmp, dtype=torch.float32, device=dev)
+    side, wss, cs = _side_ctx(dev, ws_side, (tmp,) + reads, rows)
+    wsm = _ws(ws_main if side else max(ws_main, ws_side), dev)  # no side stream: the weight gradients use it too
+    return grads, tmp, wsm, side, wss, (wss.numel() if wss is not None else 0), cs
 
 
 def _side_ctx(dev, ws_side_bytes, reads, rows=0):
@@ -1153,23 +1201,13 @@ class CpeFn(torch.autograd.Function):
             n_, C = xs.shape
             dev = xs.device
             _, n_grads, n_tmp, ws_main, ws_side, ws_conv = _sizes("cpe", n_, C)
-            grads = _grad_slab(n_grads, dev)
-            tmp = torch.empty(n_tmp, dtype=torch.float32, device=dev)
+            grads, tmp, wsm, side, wss, wss_bytes, cs = _bwd_buffers(n_grads, n_tmp, ws_main, ws_side, dev, (saved, xs, lvl.nbr27), n_)
             dxc = torch.empty_like(xs)
-            side, wss, cs = _side_ctx(dev, ws_side, (saved, tmp, xs, lvl.nbr27), n_)
-            wsm = _ws(ws_main if side else max(ws_main, ws_side), dev)  # no side stream: the weight gradients use it too
             wc = WS.get(ws_conv, dev, slot=2)
             _capi.call_raw("lotus_cpe_bwd", dy, xs, cw, wt, ctx.wk[0], g, saved, dxc, 1 if ctx.same else 0, grads, tmp, lvl.nbr27,
                            lvl.order[0], lvl.tap_plan, lvl.code[0], lvl.n_dup, n_, C, ctx.pc, wsm, wsm.numel(), wc, wc.numel(), wss,
-                           wss.numel() if wss is not None else 0, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
-            o1 = 2 * _al4(C)
-            o2 = o1 + _al4(C * C + C)
-            dg, db = grads[:C], grads[_al4(C):_al4(C) + C]
-            dlw, dlb = grads[o1:o1 + C * C].view(C, C), grads[o1 + C * C:o1 + C * C + C]
-            dcw, dcb = grads[o2:o2 + C * 27 * C].view(cw.shape), grads[o2 + C * 27 * C:o2 + C * 27 * C + C]
-            if ctx.same:
-                return dxc, None, dcw, dcb, dlw, dlb, dg, db, None, None
-            return dy, dxc, dcw, dcb, dlw, dlb, dg, db, None, None
+                           wss_bytes, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
+            return ((dxc, None) if ctx.same else (dy, dxc)) + _grad_views(grads, "cpe", C, cshape=cw.shape) + (None, None)
         xs, cw, lw, g, c, l, mean, rstd, wt = ctx.saved_tensors
         dl, dg, db = ln_bwd(dy, l, mean, rstd, g)
         return cpe_branch_bwd(dl, dy, xs, cw, ctx.wk[0], c, lvl, wt, ctx.same) + (dg, db, None, None)
@@ -1218,24 +1256,14 @@ class FfnFn(torch.autograd.Function):
             M, C = x.shape
             Hd, dev = w1.shape[0], x.device
             _, n_grads, n_tmp, ws_main, ws_side = _sizes("ffn", M, C, Hd)
-            grads = _grad_slab(n_grads, dev)
-            tmp = torch.empty(n_tmp, dtype=torch.float32, device=dev)
-            dx = torch.empty_like(x)
             dz_in = hand_in.take(dy) if hand_in is not None else None
-            dz_out, po, so = None, 0.0, 0
-            if hand_out is not None and hand_out.drop is not None:
-                po, so = hand_out.drop
-                dz_out = torch.empty_like(x)
-                hand_out.ptr, hand_out.dz = dx.data_ptr(), dz_out
-            side, wss, cs = _side_ctx(dev, ws_side, (saved, tmp, dy, dz_in), M)
-            wsm = _ws(ws_main if side else max(ws_main, ws_side), dev)  # no side stream: the weight gradients use it too
+            grads, tmp, wsm, side, wss, wss_bytes, cs = _bwd_buffers(n_grads, n_tmp, ws_main, ws_side, dev, (saved, dy, dz_in), M)
+            dx = torch.empty_like(x)
+            dz_out, po, so = Handoff.offer(hand_out, dx)
             _capi.call_raw("lotus_ffn_bwd", dy, dz_in, x, g, ctx.wk[0], ctx.wk[1], saved, dx, dz_out, po, so, grads, tmp, M, C, Hd, float(p),
-                           int(seed), mix_seed(seed, 1), ctx.pc, wsm, wsm.numel(), wss, wss.numel() if wss is not None else 0,
-                           _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
-            o1 = 2 * _al4(C)
-            o2 = o1 + _al4(Hd * C + Hd)
-            return (dx, grads[:C], grads[_al4(C):_al4(C) + C], grads[o1:o1 + Hd * C].view(Hd, C), grads[o1 + Hd * C:o1 + Hd * C + Hd],
-                    grads[o2:o2 + C * Hd].view(C, Hd), grads[o2 + C * Hd:o2 + C * Hd + C], None, None, None, None, None)
+                           int(seed), mix_seed(seed, 1), ctx.pc, wsm, wsm.numel(), wss, wss_bytes, _counters(dev), cs, _LINK, 0,
+                           _capi.stream_ptr(), side)
+            return (dx,) + _grad_views(grads, "ffn", C, Hd=Hd) + (None,) * 5
         x, g, w1, w2, n, hpre, a, mean, rstd = ctx.saved_tensors
         dn, dw1, db1, dw2, db2 = ffn_branch_bwd(dy, n, hpre, a, ctx.wk[0], ctx.wk[1], p, seed, ctx.dpath, hand_in)
         dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy, hand=hand_out)
@@ -1283,24 +1311,14 @@ class SelfAttnFn(torch.autograd.Function):
             N, C = x.shape
             dev = x.device
             _, n_grads, n_tmp, ws_main, ws_side = _sizes("self", N, C, H, lvl.npad, lvl.n_self_tiles, lvl.n_extra)
-            grads = _grad_slab(n_grads, dev)
-            tmp = torch.empty(n_tmp, dtype=torch.float32, device=dev)
-            dx = torch.empty_like(x)
             dz_in = ctx.hand_in.take(dy) if ctx.hand_in is not None else None
-            side, wss, cs = _side_ctx(dev, ws_side, (saved, tmp, dy, dz_in), N)
-            wsm = _ws(ws_main if side else max(ws_main, ws_side), dev)  # no side stream: the weight gradients use it too
+            grads, tmp, wsm, side, wss, wss_bytes, cs = _bwd_buffers(n_grads, n_tmp, ws_main, ws_side, dev, (saved, dy, dz_in), N)
+            dx = torch.empty_like(x)
             _capi.call_raw("lotus_selfattn_bwd", dy, dz_in, x, g, ctx.wk[0], qnw, qnb, knw, knb, ctx.wk[1], saved, dx, grads, tmp, lvl.gidx,
                            lvl.owner, lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, lvl.kext, lvl.ext_pos, lvl.n_extra, lvl.npad,
                            N, C, H, float(d ** -0.5), float(p), int(seed), float(attn_p), mix_seed(seed, 1), ctx.pc, wsm, wsm.numel(),
-                           wss, wss.numel() if wss is not None else 0, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
-            d4 = _al4(d)
-            o1 = 2 * _al4(C)
-            o2 = o1 + _al4(3 * C * C + 3 * C)
-            o3 = o2 + 4 * d4
-            return (dx, grads[:C], grads[_al4(C):_al4(C) + C], grads[o1:o1 + 3 * C * C].view(3 * C, C),
-                    grads[o1 + 3 * C * C:o1 + 3 * C * C + 3 * C], grads[o2:o2 + d], grads[o2 + d4:o2 + d4 + d],
-                    grads[o2 + 2 * d4:o2 + 2 * d4 + d], grads[o2 + 3 * d4:o2 + 3 * d4 + d], grads[o3:o3 + C * C].view(C, C),
-                    grads[o3 + C * C:o3 + C * C + C], None, None, None, None, None, None, None)
+                           wss, wss_bytes, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
+            return (dx,) + _grad_views(grads, "self", C, H) + (None,) * 7
         x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd = ctx.saved_tensors
         dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp = selfattn_branch_bwd(dy, n, qkv, att, lse, ctx.wk[0], (qnw, qnb), (knw, knb),
                                                                          ctx.wk[1], lvl, H, p, seed, attn_p, ctx.dpath, ctx.hand_in)
@@ -1356,31 +1374,16 @@ class CrossAttnFn(torch.autograd.Function):
             L, Cc = context.shape
             dev, G = x.device, lvl.ca_groups
             _, n_grads, n_tmp, ws_main, ws_side = _sizes("cross", N, C, H, L, Cc, lvl.n_ca_blocks, G)
-            grads = _grad_slab(n_grads, dev)
-            tmp = torch.empty(n_tmp, dtype=torch.float32, device=dev)
+            dz_in = hand_in.take(dy) if hand_in is not None else None
+            grads, tmp, wsm, side, wss, wss_bytes, cs = _bwd_buffers(n_grads, n_tmp, ws_main, ws_side, dev, (saved, dy, dz_in, context), N)
             dx = torch.empty_like(x)
             dctx = torch.empty_like(context) if ctx.needs_input_grad[1] else None
-            dz_in = hand_in.take(dy) if hand_in is not None else None
-            dz_out, po, so = None, 0.0, 0
-            if hand_out is not None and hand_out.drop is not None:
-                po, so = hand_out.drop
-                dz_out = torch.empty_like(x)
-                hand_out.ptr, hand_out.dz = dx.data_ptr(), dz_out
-            side, wss, cs = _side_ctx(dev, ws_side, (saved, tmp, dy, dz_in, context), N)
-            wsm = _ws(ws_main if side else max(ws_main, ws_side), dev)  # no side stream: the weight gradients use it too
+            dz_out, po, so = Handoff.offer(hand_out, dx)
             _capi.call_raw("lotus_crossattn_bwd", dy, dz_in, x, context, g, ctx.wk[0], ctx.wk[1], qnw, qnb, knw, knb, ctx.wk[2], saved, dx, dctx, dz_out,
                            po, so, grads, tmp, lvl.ca_tiles, lvl.ca_blocks, lvl.n_ca_blocks, G, N, C, H, L, Cc, float(d ** -0.5),
                            float(p), int(seed), float(attn_p), mix_seed(seed, 1), ctx.pc, lvl.ca_kmax, wsm, wsm.numel(), wss,
-                           wss.numel() if wss is not None else 0, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
-            d4 = _al4(d)
-            o1 = 2 * _al4(C)
-            o2 = o1 + _al4(C * C + C)
-            o3 = o2 + _al4(2 * C * Cc + 2 * C)
-            o4 = o3 + 4 * d4
-            return (dx, dctx, grads[:C], grads[_al4(C):_al4(C) + C], grads[o1:o1 + C * C].view(C, C), grads[o1 + C * C:o1 + C * C + C],
-                    grads[o2:o2 + 2 * C * Cc].view(2 * C, Cc), grads[o2 + 2 * C * Cc:o2 + 2 * C * Cc + 2 * C], grads[o3:o3 + d],
-                    grads[o3 + d4:o3 + d4 + d], grads[o3 + 2 * d4:o3 + 2 * d4 + d], grads[o3 + 3 * d4:o3 + 3 * d4 + d],
-                    grads[o4:o4 + C * C].view(C, C), grads[o4 + C * C:o4 + C * C + C], None, None, None, None, None, None, None)
+                           wss_bytes, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
+            return (dx, dctx) + _grad_views(grads, "cross", C, H, Cc=Cc) + (None,) * 7
         x, context, g, wq, wkv, qnw, qnb, knw, knb, wp, n, q, kv, att, lse, mean, rstd = ctx.saved_tensors
         N, C = x.shape
         dev = x.device
@@ -1510,28 +1513,15 @@ class CrossAttnKvFn(torch.autograd.Function):
             N, C = x.shape
             L, dev, G = kv.shape[0], x.device, lvl.ca_groups
             _, n_grads, n_tmp, ws_main, ws_side = _sizes("crosskv", N, C, H, L, lvl.n_ca_blocks, G)
-            grads = _grad_slab(n_grads, dev)
-            tmp = torch.empty(n_tmp, dtype=torch.float32, device=dev)
-            dx = torch.empty_like(x)
             dz_in = hand_in.take(dy) if hand_in is not None else None
-            dz_out, po, so = None, 0.0, 0
-            if hand_out is not None and hand_out.drop is not None:
-                po, so = hand_out.drop
-                dz_out = torch.empty_like(x)
-                hand_out.ptr, hand_out.dz = dx.data_ptr(), dz_out
-            side, wss, cs = _side_ctx(dev, ws_side, (saved, tmp, dy, dz_in), N)
-            wsm = _ws(ws_main if side else max(ws_main, ws_side), dev)
+            grads, tmp, wsm, side, wss, wss_bytes, cs = _bwd_buffers(n_grads, n_tmp, ws_main, ws_side, dev, (saved, dy, dz_in), N)
+            dx = torch.empty_like(x)
+            dz_out, po, so = Handoff.offer(hand_out, dx)
             _capi.call_raw("lotus_crossattn_kv_bwd", dy, dz_in, x, kv, kv.stride(0), g, ctx.wk[0], qnw, qnb, knw, knb, ctx.wk[1], saved, dx, dkv,
                            dkv.stride(0), dz_out, po, so, grads, tmp, lvl.ca_tiles, lvl.ca_blocks, lvl.n_ca_blocks, G, N, C, H, L,
                            float(d ** -0.5), float(p), int(seed), float(attn_p), mix_seed(seed, 1), ctx.pc, lvl.ca_kmax, wsm, wsm.numel(),
-                           wss, wss.numel() if wss is not None else 0, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
-            d4 = _al4(d)
-            o1 = 2 * _al4(C)
-            o2 = o1 + _al4(C * C + C)
-            o3 = o2 + 4 * d4
-            return (dx, dkv, grads[:C], grads[_al4(C):_al4(C) + C], grads[o1:o1 + C * C].view(C, C), grads[o1 + C * C:o1 + C * C + C],
-                    grads[o2:o2 + d], grads[o2 + d4:o2 + d4 + d], grads[o2 + 2 * d4:o2 + 2 * d4 + d], grads[o2 + 3 * d4:o2 + 3 * d4 + d],
-                    grads[o3:o3 + C * C].view(C, C), grads[o3 + C * C:o3 + C * C + C]) + (None,) * 9
+                           wss, wss_bytes, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
+            return (dx, dkv) + _grad_views(grads, "crosskv", C, H) + (None,) * 9
         x, kv, g, wq, qnw, qnb, knw, knb, wp, n, q, att, lse, mean, rstd = ctx.saved_tensors
         N, C = x.shape
         dev = x.device
@@ -1567,13 +1557,8 @@ class CrossAttnKvFn(torch.autograd.Function):
 # them again for the next sub-block (smaller live footprint in the 256 MB Infinity Cache / TLB).
 _PAIR = {"0": False, "1": True}.get(os.environ.get("LOTUS_PAIR", "auto"), "auto")
 _PAIR_AUTO_ROWS = 40000
-_PP = None  # index tables of csrc/blocks.cpp: enum PairPtr / PairInt (kept in step by tests/test_gpu_round4.py)
-_PP_NAMES = ("X XS KV Y ACTS SAVED CW CWP CB LW LB G0 B0 G1 B1 WQKV BQKV QNW QNB KNW KNB WP BP G2 B2 W1 B1F W2 B2F G3 B3 WQ BQ CQNW CQNB "
-             "CKNW CKNB CWP2 CBP2 G4 B4 W3 B3F W4 B4F NBR27 ORDER0 TAPPLAN CODE0 GIDX OWNER STILES SBLOCKS KEXT EXTPOS CATILES CABLOCKS WS_MAIN "
-             "WS_SIDE WS_CONV CNT_MAIN CNT_SIDE STREAM SIDE DY DX DXS DKV GRADS TMP").split()
-_PI_NAMES = ("M C H HD NPAD NSTILES NEXTRA L NCATILES NCABLOCKS G KMAX NDUP SAME PREC KV_LD DKV_LD WS_MAIN WS_SIDE WS_CONV LINK SEED_SELF "
-             "SEED_FFN1 SEED_CROSS SEED_FFN2").split()
-# parameter slots of PairFn in call order -> their PairPtr names
+_PP = None  # name -> index tables of the pair's argument arrays, from the library's own lists (csrc/blocks.cpp PAIR_PTRS / PAIR_INTS)
+# parameter slots of PairFn in call order -> their names in the library's pointer list
 _PAIR_PARAM_SLOTS = ("CW CB LW LB G0 B0 G1 B1 WQKV BQKV QNW QNB KNW KNB WP BP G2 B2 W1 B1F W2 B2F G3 B3 WQ BQ CQNW CQNB CKNW CKNB CWP2 CBP2 "
                      "G4 B4 W3 B3F W4 B4F").split()
 _PAIR_LINEAR = (2, 8, 14, 18, 20, 24, 30, 34, 36)   # indices (in that order) of the dense-layer weights: candidates for bf16 shadows
@@ -1604,25 +1589,10 @@ def _pair_tables():
     global _PP
     if _PP is None:
         import numpy as np
-        assert query("lotus_pair_nptr") == len(_PP_NAMES) and query("lotus_pair_nint") == len(_PI_NAMES), \
-            "ops._PP_NAMES / _PI_NAMES are out of step with enum PairPtr / PairInt of csrc/blocks.cpp"
-        _PP = (np, {n: i for i, n in enumerate(_PP_NAMES)}, {n: i for i, n in enumerate(_PI_NAMES)},
-               [_PP_NAMES.index(n) for n in _PAIR_PARAM_SLOTS])
+        names = [query(q) for q in ("lotus_pair_ptr_names", "lotus_pair_int_names")]
+        pp, pi = ({n: i for i, n in enumerate((s if isinstance(s, str) else s.decode()).split())} for s in names)
+        _PP = (np, pp, pi, [pp[n] for n in _PAIR_PARAM_SLOTS])   # (a slot name the library does not list: KeyError with the name)
     return _PP
-
-
-def _pair_grad_sizes(C, H, Hd):
-    key = ("pairgrads", C, H, Hd)
-    v = _SIZE_CACHE.get(key)
-    if v is None:
-        d = C // H
-        assert C % 4 == 0 and d % 4 == 0 and Hd % 4 == 0
-        cpe = [C, C, C * C, C, 27 * C * C, C]
-        att = [C, C, 3 * C * C, 3 * C, d, d, d, d, C * C, C]
-        ffn = [C, C, Hd * C, Hd, C * Hd, C]
-        ca = [C, C, C * C, C, d, d, d, d, C * C, C]
-        v = _SIZE_CACHE[key] = cpe + att + ffn + ca + ffn
-    return v
 
 
 class PairFn(torch.autograd.Function):
@@ -1651,8 +1621,8 @@ class PairFn(torch.autograd.Function):
         # dense-layer weights: bf16 shadows when this forward runs in shadow mode and every one of them has a shadow
         lin = [params[i] for i in _PAIR_LINEAR]
         link, pc = _wk(*lin)
-        P = np.zeros(len(_PP_NAMES), dtype=np.uint64)
-        I = np.zeros(len(_PI_NAMES), dtype=np.uint64)
+        P = np.zeros(len(PP), dtype=np.uint64)
+        I = np.zeros(len(PI), dtype=np.uint64)
         for slot, t in zip(slots, params):
             P[slot] = t.data_ptr()
         for i, t in zip(_PAIR_LINEAR, link):
@@ -1691,30 +1661,20 @@ class PairFn(torch.autograd.Function):
         dy = dy.contiguous()
         _, _, n_grads, n_tmp, ws_main, ws_side, ws_conv = _sizes(
             "pair", M, C, H, Hd, lvl.npad, lvl.n_self_tiles, lvl.n_extra, L, lvl_ca.n_ca_blocks, lvl_ca.ca_groups)
-        grads = _grad_slab(n_grads, dev)
-        tmp = torch.empty(n_tmp, dtype=torch.float32, device=dev)
+        grads, tmp, wsm, side, wss, wss_bytes, cs = _bwd_buffers(n_grads, n_tmp, ws_main, ws_side, dev, (saved, acts, dy, xs, kv, lvl.nbr27), M)
         dx = torch.empty_like(dy)
         dxs = None if same else torch.empty_like(xs)
         dkv = bank.grad_slice(bidx)
-        side, wss, cs = _side_ctx(dev, ws_side, (saved, acts, tmp, dy, xs, kv, lvl.nbr27), M)
-        wsm = _ws(ws_main if side else max(ws_main, ws_side), dev)
         wc = WS.get(ws_conv, dev, slot=2)
         P[PP["DY"]], P[PP["DX"]], P[PP["DXS"]] = dy.data_ptr(), dx.data_ptr(), (0 if dxs is None else dxs.data_ptr())
         P[PP["DKV"]], P[PP["GRADS"]], P[PP["TMP"]] = dkv.data_ptr(), grads.data_ptr(), tmp.data_ptr()
         P[PP["WS_MAIN"]], P[PP["WS_CONV"]], P[PP["WS_SIDE"]] = wsm.data_ptr(), wc.data_ptr(), (0 if wss is None else wss.data_ptr())
         P[PP["CNT_MAIN"]], P[PP["CNT_SIDE"]] = _counters(dev).data_ptr(), (0 if cs is None else cs.data_ptr())
         P[PP["STREAM"]], P[PP["SIDE"]] = _capi.stream_ptr(), side
-        I[PI["WS_MAIN"]], I[PI["WS_CONV"]], I[PI["WS_SIDE"]] = wsm.numel(), wc.numel(), (0 if wss is None else wss.numel())
+        I[PI["WS_MAIN"]], I[PI["WS_CONV"]], I[PI["WS_SIDE"]] = wsm.numel(), wc.numel(), wss_bytes
         I[PI["DKV_LD"]], I[PI["LINK"]] = dkv.stride(0), _LINK
         _capi.call_raw("lotus_pair_bwd", P.ctypes.data, I.ctypes.data, F.ctypes.data)
-        g = grads.split(_pair_grad_sizes(C, H, Hd))
-        cw = params[0]
-        out = (g[4].view(cw.shape), g[5], g[2].view(C, C), g[3], g[0], g[1],                                  # cpe
-               g[6], g[7], g[8].view(3 * C, C), g[9], g[10], g[11], g[12], g[13], g[14].view(C, C), g[15],     # self-attention
-               g[16], g[17], g[18].view(Hd, C), g[19], g[20].view(C, Hd), g[21],                               # mlp
-               g[22], g[23], g[24].view(C, C), g[25], g[26], g[27], g[28], g[29], g[30].view(C, C), g[31],     # cross-attention
-               g[32], g[33], g[34].view(Hd, C), g[35], g[36].view(C, Hd), g[37])                               # mlp
-        return (dx, dxs, dkv, None) + out + (None,)
+        return (dx, dxs, dkv, None) + _grad_views(grads, "pair", C, H, Hd, cshape=params[0].shape) + (None,)
 
 
 class StemFn(torch.autograd.Function):
