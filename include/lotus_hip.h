@@ -181,6 +181,12 @@ size_t lotus_linear_wgrad_workspace(int M, int N, int K);
 int lotus_linear_wgrad(const lotus_act_t* dy, const lotus_act_t* x, float* dw, float* db, int M, int N, int K,
                        int accumulate, int precision, void* workspace, size_t workspace_bytes, void* counters,
                        void* stream);
+/* Diagnostic: the kernel the calling thread's last dense product (the four entry points above, the tap-grouped convolution)
+ * was given to, recorded when the launch is chosen (also where the launch then fails).  out[8] = {family: 1 gemm_kernel |
+ * 2 gemm_dma_kernel | 3 gemm_dma_tap_kernel, BM, BN, BK of the block tile, nz split count, FAST (1: vector loads and
+ * stores, 0: per-element guarded), fused split-K (1: last-arrival reduction, 0: none or a second launch), staging-ring
+ * depth (family 1) or LDS stages (2, 3)}.  An entry point that launches several products leaves the last one. */
+int lotus_dense_last_route(int* out);
 
 /* ---- submanifold sparse convolution (spconv.SubMConv3d, model.py:615-622, :844-853) -------- */
 /* mode 0 fwd: y[n][cout] = sum_t W[:,t,:] x[nbr[t][.]] + bias (+ add); mode 1 dgrad: x = dy, y = dx.

@@ -387,9 +387,12 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
         __syncthreads();
       }
     }
-    // drain: the RD slabs in the ring (all inside the range), then the < RD slabs fetched on the way
+    // drain: the RD slabs in the ring (all inside the range), then the <= RD slabs fetched on the way.  (The loop above leaves
+    // less than 2 RD slabs of DEPTH, which is up to 2 RD slabs when the last one is partial: 2 RD - 1 passes dropped that tail —
+    // a reduction of 196 lost its last 4 products.  Every width of the model is a multiple of RD * BK; found by the split
+    // ranges 448 + 324 of tests/dense_edges.py.)
 #pragma unroll
-    for (int d = 0; d < 2 * RD - 1; ++d) {
+    for (int d = 0; d < 2 * RD; ++d) {
       const int kk = k0 + d * BK;
       if (kk < kend) {
         if (d < RD && kk + RD * BK < kend) {
@@ -597,15 +600,24 @@ static inline int vec_ok(const void* p, long ld) { return (((uintptr_t)p) % 16 =
 #define GEMM_GO_RD(BM_, BN_, BK_, PREC_, grid_, RD_)                                                                             \
   do {                                                                                                                           \
     using TB_ = std::conditional_t<SUM_A, act_t, float>;                                                                         \
+    /* (the route record sits beside each launch: a combination that launches nothing records nothing) */                        \
+    auto note_ = [&] { lotus_note_dense_route(1, BM_, BN_, BK_, nz, FAST, FAST && p.cnt && nz > 1, RD_); };                      \
     if constexpr (LOTUS_ACT_IS_BF16 && !SUM_A) {                                                                                 \
       if (p.b_act) { /* bf16 weight shadow: half the weight bytes per block, no conversion while staging */                      \
         if constexpr (PREC_ == 1 && FAST) {                                                                                      \
+          note_();                                                                                                               \
           if (p.c_float) LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, act_t, float, RD_>), grid_, block, 0, st, p); \
           else LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, act_t, act_t, RD_>), grid_, block, 0, st, p); \
         }                                                                                                                        \
-      } else if (p.c_float) LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, TB_, float, RD_>), grid_, block, 0, st, p); \
-      else LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, TB_, act_t, RD_>), grid_, block, 0, st, p);   \
+      } else if (p.c_float) {                                                                                                    \
+        note_();                                                                                                                 \
+        LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, TB_, float, RD_>), grid_, block, 0, st, p); \
+      } else {                                                                                                                   \
+        note_();                                                                                                                 \
+        LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, TB_, act_t, RD_>), grid_, block, 0, st, p); \
+      }                                                                                                                          \
     } else {                                                                                                                     \
+      note_();                                                                                                                   \
       LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, TB_, float, RD_>), grid_, block, 0, st, p);      \
     }                                                                                                                            \
   } while (0)
@@ -677,6 +689,7 @@ static int launch_gemm_t(GemmP& p, int nz, hipStream_t st) {
     const int rd = SUM_A ? 1 : (blocks_eff * nz <= kF32RingMaxBlocks ? 2 : 1);
     if (p.tap_rows) {
       if constexpr (A_KC && !SUM_A && FAST && !LOTUS_ACT_IS_BF16) {
+        lotus_note_dense_route(1, 64, 64, bk, nz, FAST, 0, 2);
         if (bk == 64) LOTUS_LAUNCH((gemm_kernel<64, 64, 64, A_KC, B_KC, SUM_A, FAST, 0, act_t, float, float, 2, true>), g64, block, 0, st, p);
         else if (bk == 32) LOTUS_LAUNCH((gemm_kernel<64, 64, 32, A_KC, B_KC, SUM_A, FAST, 0, act_t, float, float, 2, true>), g64, block, 0, st, p);
         else LOTUS_LAUNCH((gemm_kernel<64, 64, 16, A_KC, B_KC, SUM_A, FAST, 0, act_t, float, float, 2, true>), g64, block, 0, st, p);
@@ -963,6 +976,14 @@ int lotus_linear_dgrad_ln(const act_t* dy, const float* w, const act_t* x, const
   return rc;
 }
 
+// The route of the calling thread's last dense product (fwd / dgrad / dgrad_ln / wgrad, the tap-grouped convolution): out[8] =
+// {family, BM, BN, BK, nz, FAST, fused split-K, ring depth | stages}.  Diagnostic: what the tests assert their kernel with.
+int lotus_dense_last_route(int* out) {
+  LOTUS_CHECK_ARG(out, "lotus_dense_last_route: out is null");
+  for (int i = 0; i < 8; ++i) out[i] = lotus_tls_dense_route[i];
+  return LOTUS_OK;
+}
+
 static int wgrad_splits(int M, int N, int K) {
   if (const int dz = gemm_dma_wgrad_splits(M, N, K)) return dz;  // tall products on the LDS-DMA kernels: their own tiling
   int nz = 1;
@@ -1003,8 +1024,10 @@ int lotus_linear_wgrad(const act_t* dy, const act_t* x, float* dw, float* db, in
   set_drop(p, 0.f, 0);
   constexpr int fuse_max = 4;  // measured: nz 4 fused 46 -> 41 us, nz 16 fused 42 -> 51 us
   const long wtiles = (long)cdiv(N, 64) * cdiv(K, 64);
-  if (!direct && counters && splitk_fused_enabled() && nz <= fuse_max && wtiles <= LOTUS_SPLITK_MAX_TILES) {
-    // few splits: the last block of every output tile sums the partials (and the bias partials) itself
+  if (!direct && counters && splitk_fused_enabled() && nz > 1 && nz <= fuse_max && wtiles <= LOTUS_SPLITK_MAX_TILES) {
+    // few splits: the last block of every output tile sums the partials (and the bias partials) itself.  (Not one split:
+    // a grid without a z axis has no last-arrival tail, so an accumulating call added dw in the epilogue and left its bias
+    // partial in the workspace — db was never touched.  One split that accumulates goes through lotus_reduce_parts below.)
     GemmP q = p;
     q.C = dw; q.part = part; q.part_stride = (long)slab; q.cnt = (unsigned*)counters;
     q.bias_part = db ? part + (size_t)N * K : nullptr; q.bias_stride = (long)slab; q.bias_out = db; q.accumulate = accumulate;

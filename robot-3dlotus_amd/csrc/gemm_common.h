@@ -3,6 +3,16 @@
 #pragma once
 #include "mma.h"
 
+// Which kernel the calling thread's last dense product was given to, written where the launch is chosen and before it is
+// attempted (so it is set on a machine without a device too): {family 1 gemm_kernel | 2 gemm_dma_kernel | 3 gemm_dma_tap_kernel,
+// BM, BN, BK, nz, FAST, fused split-K, staging-ring depth (family 1) or LDS stages (2, 3)}.  Library-internal like
+// lotus_tls_stop_event (and `__thread` for the same reason); lotus_dense_last_route copies it out.
+extern __attribute__((visibility("hidden"))) __thread int lotus_tls_dense_route[8];
+static inline void lotus_note_dense_route(int family, int bm, int bn, int bk, int nz, int fast, int fused, int depth) {
+  int* r = lotus_tls_dense_route;
+  r[0] = family; r[1] = bm; r[2] = bn; r[3] = bk; r[4] = nz; r[5] = fast; r[6] = fused; r[7] = depth;
+}
+
 namespace LOTUS_NS {
 
 struct GemmP {

@@ -58,6 +58,7 @@ int launch_gemm_dma(GemmP& p, int layout, int nz, hipStream_t st) {
 #define DMA_GO(BM, BN, BK, NST, XKC, WKC, SUMA)                                                                         \
   do {                                                                                                                  \
     dim3 grid(cdiv(p.N, BN), cdiv(p.M, BM), nz);                                                                        \
+    lotus_note_dense_route(2, BM, BN, BK, nz, 1, p.cnt && nz > 1, NST);                                                 \
     if (epi) LOTUS_LAUNCH((gemm_dma_kernel<BM, BN, BK, NST, XKC, WKC, SUMA, 1>), grid, block, 0, st, p);                \
     else LOTUS_LAUNCH((gemm_dma_kernel<BM, BN, BK, NST, XKC, WKC, SUMA, 0>), grid, block, 0, st, p);                    \
   } while (0)
@@ -68,6 +69,7 @@ int launch_gemm_dma(GemmP& p, int layout, int nz, hipStream_t st) {
       else DMA_GO(128, 64, 32, 2, true, true, false);
     } else if (layout == 1 && ln) {
       dim3 grid(1, cdiv(p.M, 128), 1);
+      lotus_note_dense_route(2, 128, wide ? 128 : 64, bk, 1, 1, 0, wide ? 3 : 2);
       if (wide) LOTUS_LAUNCH((gemm_dma_kernel<128, 128, 16, 3, true, false, false, 2>), grid, block, 0, st, p);
       else LOTUS_LAUNCH((gemm_dma_kernel<128, 64, 32, 2, true, false, false, 2>), grid, block, 0, st, p);
     } else if (layout == 1) {
@@ -106,6 +108,7 @@ int launch_gemm_dma_tap(GemmP& p, int layout, hipStream_t st) {
       return LOTUS_GEMM_DMA_NA;
     p.klen = p.K;
     const dim3 grid(cdiv(p.N, wide ? 128 : 64), 27 * cdiv(p.tap_rows, 128)), block(256);
+    lotus_note_dense_route(3, 128, wide ? 128 : 64, bk, 1, 1, 0, wide ? 3 : 2);
     if (layout == 0) {
       if (wide) LOTUS_LAUNCH((gemm_dma_tap_kernel<128, 128, 16, 3, true>), grid, block, 0, st, p);
       else LOTUS_LAUNCH((gemm_dma_tap_kernel<128, 64, 32, 2, true>), grid, block, 0, st, p);

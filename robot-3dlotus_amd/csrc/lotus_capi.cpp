@@ -8,6 +8,9 @@
 static thread_local char g_err[512] = "";
 __attribute__((visibility("hidden"))) __thread hipEvent_t lotus_tls_stop_event = nullptr;  // see LOTUS_LAUNCH (common.h)
 
+// route of the calling thread's last dense product (gemm_common.h: lotus_note_dense_route; read by lotus_dense_last_route)
+__attribute__((visibility("hidden"))) __thread int lotus_tls_dense_route[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
 void lotus_set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);

@@ -13,6 +13,8 @@ backward that chains the HIP kernels (fused epilogues, no temporaries beyond wha
                                                                    euler / quat rotations (csrc/reg_head.hip)
 PyTorch provides device memory, the stream and the autograd graph; all arithmetic is in the kernels.
 """
+import collections
+import ctypes
 import os
 
 import torch
@@ -25,6 +27,19 @@ BN_EPS, BN_MOMENTUM = 1e-3, 0.01
 CALL_LOG = None  # bench.py sets this to a list to record the (kind, M, N, K) of every dense launch
 EVENT_LOG = None  # ... and this to a list to get (kind, M, N, K, start event, end event) of every dense launch, recorded on
                   # the stream the launch went to (the timed quantities of bench.py's in-step roofline figure)
+
+
+DenseRoute = collections.namedtuple("DenseRoute", "family bm bn bk nz fast fused depth")
+FAMILY_GEMM, FAMILY_GEMM_DMA, FAMILY_GEMM_DMA_TAP = 1, 2, 3
+
+
+def last_dense_route():
+    """The kernel this thread's last dense product was given to (lotus_dense_last_route): family 1 gemm_kernel, 2
+    gemm_dma_kernel, 3 gemm_dma_tap_kernel; block tile; split count; FAST or guarded form; fused split-K; staging-ring depth
+    (family 1) or LDS stages.  Set when the launch is chosen, so it is there after a launch that failed, too."""
+    out = (ctypes.c_int * 8)()
+    _capi.call_raw("lotus_dense_last_route", ctypes.addressof(out))
+    return DenseRoute(*out)
 
 
 class _Timed:

@@ -214,6 +214,10 @@ def test_launching_entry_point_returns_an_error_without_a_device(built):
     a, w, y = (np.zeros(n, dtype=np.float32) for n in (100 * 64, 32 * 64, 100 * 32))
     rc = L.fn["lotus_linear_fwd"](a.ctypes.data, w.ctypes.data, None, None, y.ctypes.data, None, 100, 32, 64, 0, 0.0, 0, 0, None, 0, None, None)
     assert rc == -2 and b"launch failed" in L.fn["lotus_last_error"]()
-    a2, w2, y2 = (np.zeros(n, dtype=np.float32) for n in (20000 * 64, 128 * 64, 20000 * 128))   # the LDS-DMA kernels' host path
-    rc = L.fn["lotus_linear_fwd"](a2.ctypes.data, w2.ctypes.data, None, None, y2.ctypes.data, None, 20000, 128, 64, 0, 0.0, 0, 0, None, 0, None, None)
+    route = (ctypes.c_int * 8)()
+    assert L.fn["lotus_dense_last_route"](ctypes.addressof(route)) == 0 and route[0] == 1      # gemm_kernel
+    # the LDS-DMA kernels' host path: 157 x 4 = 628 blocks of 128 x 128 (157 x 1 at 128 output columns stay on gemm_kernel)
+    a2, w2, y2 = (np.zeros(n, dtype=np.float32) for n in (20000 * 64, 512 * 64, 20000 * 512))
+    rc = L.fn["lotus_linear_fwd"](a2.ctypes.data, w2.ctypes.data, None, None, y2.ctypes.data, None, 20000, 512, 64, 0, 0.0, 0, 0, None, 0, None, None)
     assert rc == -2
+    assert L.fn["lotus_dense_last_route"](ctypes.addressof(route)) == 0 and list(route)[:4] == [2, 128, 128, 16], list(route)
