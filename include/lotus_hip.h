@@ -288,6 +288,18 @@ int lotus_batchnorm_bwd_stats(const lotus_act_t* dy, const lotus_act_t* x, const
 int lotus_batchnorm_bwd_apply(const lotus_act_t* dy, const lotus_act_t* x, const float* mean, const float* invstd,
                               const float* gamma, const float* beta, const double* sums, lotus_act_t* dx, float* dgamma,
                               float* dbeta, int M, int C, int act, int train, int accumulate, void* stream);
+/* Diagnostic, host only (nothing is launched): the launch plan of the kernels above for M rows of width C, computed by the helpers
+ * the launches themselves use.  Every LayerNorm / BatchNorm entry point and query refuses C <= 0 (LOTUS_E_ARG; the size queries
+ * return 0); a width the launch would refuse is refused here too.  out, by kind:
+ *   0 LayerNorm forward:   out[4] = {lanes per row, float4 quads per lane, rows per block, grid}
+ *   1 LayerNorm backward:  out[5] = {lanes per row, quads per lane, rows per block, grid (= partial rows, lotus_layernorm_bwd_parts),
+ *                                    passes of the grid-stride row loop}
+ *   2 BatchNorm statistics in two launches (lotus_batchnorm_stats, _bwd_stats), 3 fused (the *_stats_fused entry points):
+ *                          out[7] = {row slots per block, threads per row, column slabs, grid, groups of the last-arrival reduction
+ *                                    (0 for kind 2), rows every row slot walks, row slots that walk one row more}
+ *   4 BatchNorm apply (lotus_batchnorm_apply, _apply_sums, _bwd_apply): out[3] = {grid, blocks per column period, 1 when the
+ *                                    4096-block cap was hit before rounding to whole periods} */
+int lotus_norm_plan(int kind, int M, int C, int* out);
 
 /* ---- attention ---------------------------------------------------------------------------- */
 /* flash_attn_varlen_qkvpacked_func (model.py:543-549) and flash_attn_varlen_kvpacked_func
@@ -598,6 +610,12 @@ int lotus_adabn_bwd_apply_sums(const float* dy, const float* x, const float* mea
                                int M, int C, int act, void* stream);
 /* PDNorm.modulation[0] = nn.SiLU (model.py:276-278): y = SiLU(x), or y = dy SiLU'(x) when dy is given */
 int lotus_ada_silu(const float* x, const float* dy, float* y, int n, void* stream);
+/* Diagnostic, host only: the launch plan for M rows in B clouds at width C, from the helpers the launches use.  out[6] = {row
+ * chunks per cloud G (the workspace is B G 2C floats), grid of the elementwise apply kernels (lotus_adabn_apply, _bwd), grid of the
+ * column-period apply kernels (lotus_adabn_apply_sums, _bwd_apply_sums), 1 when the 4096-block cap was hit, lanes per row and
+ * quads per lane of the LayerNorm site (0, 0: lotus_adaln_* refuse the width, the BatchNorm sites take it)}.  C <= 0, C % 4 != 0,
+ * C > 4096 or B <= 0: LOTUS_E_ARG.  Every AdaNorm entry point refuses C <= 0; lotus_adanorm_workspace then returns 0. */
+int lotus_adanorm_plan(int M, int B, int C, int* out);
 
 /* ---- regression action head (pos_pred_type 'heatmap_mlp', rot_pred_type 'euler' / 'quat'; fp32 activations only, no bf16
  * twin) ---------------------------------------------------------------------------------------------------------------- */

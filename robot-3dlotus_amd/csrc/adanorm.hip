@@ -453,7 +453,7 @@ __global__ __launch_bounds__(256) void ada_silu_kernel(const float* __restrict__
 }
 
 static int ada_geometry(int C, int* LPR, int* NV) {  // = ln_geometry of norm.hip
-  if (C % 4) return -1;
+  if (C <= 0 || C % 4) return -1;
   const int c4 = C / 4;
   int lpr = 64;
   if (c4 <= 16) lpr = 16;
@@ -471,8 +471,9 @@ static int ada_chunks(int M, int B) {
   return g < 1 ? 1 : (g > 64 ? 64 : g);
 }
 
-static int ada_grid(long total4) {
+static int ada_grid(long total4, int* capped_out = nullptr) {
   long g = (total4 + 511) / 512;
+  if (capped_out) *capped_out = g > 4096;
   return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
@@ -492,7 +493,22 @@ using namespace LOTUS_NS;
 extern "C" {
 
 size_t lotus_adanorm_workspace(int M, int B, int C) {
-  return (size_t)(B > 0 ? B : 1) * ada_chunks(M, B) * 2 * (C > 0 ? C : 1) * sizeof(float);
+  if (C <= 0) return 0;
+  return (size_t)(B > 0 ? B : 1) * ada_chunks(M, B) * 2 * C * sizeof(float);
+}
+
+// The launch plan of the kernels below for M rows in B clouds at width C, from the helpers the launches themselves use:
+// out[6] = {row chunks per cloud G, grid of the elementwise apply kernels, grid of the column-period apply kernels (the split
+// BatchNorm), 1 when the 4096-block cap was hit, lanes per row, quads per lane of the LayerNorm site (0, 0: the LayerNorm
+// entry points refuse the width, the BatchNorm ones take it)}.
+int lotus_adanorm_plan(int M, int B, int C, int* out) {
+  LOTUS_CHECK_ARG(out && M >= 0 && B > 0 && C > 0 && C % 4 == 0 && C <= 4096, "lotus_adanorm_plan: bad arguments (B=%d, C=%d)", B, C);
+  const long total4 = (long)M * C / 4;
+  out[0] = ada_chunks(M, B);
+  out[1] = ada_grid(total4, out + 3);
+  out[2] = ada_cols_grid(total4, C);
+  if (ada_geometry(C, out + 4, out + 5)) out[4] = out[5] = 0;
+  return LOTUS_OK;
 }
 
 int lotus_adaln_fwd(const float* x, const float* res, const float* gamma, const float* beta, const float* mod, int mod_ld,
@@ -528,7 +544,7 @@ int lotus_adaln_bwd(const float* dy, const float* x, const float* mean, const fl
 
 int lotus_adabn_apply(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const float* mod,
                       int mod_ld, const int* off, int B, float* y, int M, int C, int act, void* stream) {
-  LOTUS_CHECK_ARG(x && mean && invstd && gamma && beta && mod && off && y && M >= 0 && B > 0 && C % 4 == 0 && mod_ld >= 2 * C,
+  LOTUS_CHECK_ARG(x && mean && invstd && gamma && beta && mod && off && y && M >= 0 && B > 0 && C > 0 && C % 4 == 0 && mod_ld >= 2 * C,
                   "lotus_adabn_apply: bad arguments");
   if (M == 0) return LOTUS_OK;
   AdaBnP p;
@@ -544,7 +560,7 @@ int lotus_adabn_bwd(const float* dy, const float* x, const float* mean, const fl
                     const float* mod, int mod_ld, const int* off, int B, float* dx, float* dgamma, float* dbeta, float* dmod,
                     int dmod_ld, int M, int C, int act, int training, void* workspace, size_t workspace_bytes, void* stream) {
   LOTUS_CHECK_ARG(dy && x && mean && invstd && gamma && beta && mod && off && dx && dgamma && dbeta && dmod && M >= 0 && B > 0 &&
-                  C % 4 == 0 && C <= 4096 && mod_ld >= 2 * C && dmod_ld >= 2 * C, "lotus_adabn_bwd: bad arguments");
+                  C > 0 && C % 4 == 0 && C <= 4096 && mod_ld >= 2 * C && dmod_ld >= 2 * C, "lotus_adabn_bwd: bad arguments");
   LOTUS_CHECK_ARG(workspace && workspace_bytes >= lotus_adanorm_workspace(M, B, C), "lotus_adabn_bwd: workspace too small");
   AdaBnP p;
   memset(&p, 0, sizeof(p));

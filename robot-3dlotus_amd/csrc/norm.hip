@@ -200,7 +200,7 @@ __global__ __launch_bounds__(1024) void colpart_reduce_kernel(const float* __res
 }
 
 static int ln_geometry(int C, int* LPR, int* NV) {
-  if (C % 4) return -1;
+  if (C <= 0 || C % 4) return -1;
   const int c4 = C / 4;
   int lpr = 64;
   if (c4 <= 16) lpr = 16;
@@ -215,7 +215,7 @@ static int ln_geometry(int C, int* LPR, int* NV) {
 // backward geometry: as few lanes per row as 4 float4 per lane allow — every lane then has 8 independent 16-byte
 // loads (x, dy) in flight per row instead of 2, which is what the HBM latency needs at 8-16 waves per CU
 static int ln_geometry_bwd(int C, int* LPR, int* NV) {
-  if (C % 4) return -1;
+  if (C <= 0 || C % 4) return -1;
   const int c4 = C / 4;
   int lpr = 64;
   while (lpr > 4 && c4 <= (lpr / 2) * 4) lpr /= 2;
@@ -230,6 +230,9 @@ static int ln_geometry_bwd(int C, int* LPR, int* NV) {
 #define BN_GS 16         // blocks per group of the fused (last-arrival) statistics reduction
 #define BN_FUSED_MAX_GRID 256
 #define BN_COUNTERS (1 + BN_FUSED_MAX_GRID / BN_GS)
+// threads per row of bn_stat_kernel for C / 4 column quads (256 / bn_tpr row slots per block; more than 256 quads: column slabs)
+__host__ __device__ static inline int bn_tpr(int c4) { return c4 < 256 ? c4 : 256; }
+__host__ __device__ static inline int bn_rslots(int c4) { return 256 / bn_tpr(c4); }  // rows a block walks side by side
 // Column statistics in double: per-block partial (sum, sumsq) -> fixed-order reduction.
 struct BnStatP {
   const act_t* x;     // [M][C]
@@ -256,8 +259,8 @@ __global__ __launch_bounds__(256) void bn_stat_kernel(BnStatP p) {
   LOTUS_T_PRIO();
   extern __shared__ double dred[];  // [rslots][2][C]
   const int c4 = p.C / 4;
-  const int tpr = c4 < 256 ? c4 : 256;  // threads per row
-  const int rslots = 256 / tpr;
+  const int tpr = bn_tpr(c4);  // threads per row
+  const int rslots = bn_rslots(c4);
   const int rslot = threadIdx.x / tpr, l = threadIdx.x % tpr;
   const bool live = rslot < rslots;
   for (int q0 = 0; q0 < c4; q0 += tpr) {
@@ -583,23 +586,24 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(BnApplyP p) {
 
 // grid of bn_apply_kernel: ~2 float4 per thread, at most 4096 blocks, and gridDim.x * 256 a multiple of C / 4 (a thread
 // then stays on one column quad)
-static int bn_apply_grid(long total4, int C) {
+static int bn_apply_grid(long total4, int C, int* unit_out = nullptr, int* capped_out = nullptr) {
   const int c4 = C / 4;
   int a = 256, b = c4;
   while (b) { const int t = a % b; a = b; b = t; }   // a = gcd(256, c4)
   const int unit = c4 / a;                             // blocks per column period
   long g = (total4 + 511) / 512;
+  const int capped = g > 4096;
   if (g > 4096) g = 4096;
   if (g < 1) g = 1;
   g = (g + unit - 1) / unit * unit;
+  if (unit_out) *unit_out = unit;
+  if (capped_out) *capped_out = capped;
   return (int)g;
 }
 
 #define BN_MAX_GRID 512
 static int bn_grid(int M, int C) {
-  const int c4 = C / 4;
-  const int tpr = c4 < 256 ? c4 : 256;
-  const int rslots = 256 / tpr;
+  const int rslots = bn_rslots(C / 4);
   // 16 rows per thread.  Measured in the step: 16 / 4 / 2 rows -> 868 / 861 / 850 samples/s — more, smaller blocks raise the
   // stand-alone rate of this kernel but feed more partials to the fixed-order reduction behind it
   constexpr int rows = 16;
@@ -609,9 +613,7 @@ static int bn_grid(int M, int C) {
   return g;
 }
 static size_t bn_dyn_lds(int C) {
-  const int c4 = C / 4;
-  const int tpr = c4 < 256 ? c4 : 256;
-  size_t n = (size_t)(256 / tpr) * 2 * C;
+  size_t n = (size_t)bn_rslots(C / 4) * 2 * C;
   if (n < 256) n = 256;  // the fused reduction stages 256 partial sums
   return n * sizeof(double);
 }
@@ -621,6 +623,8 @@ static int bn_grid_fused(int M, int C) {
   const int g = bn_grid(M, C);
   return g > BN_FUSED_MAX_GRID ? BN_FUSED_MAX_GRID : g;
 }
+
+static int ln_fwd_grid(int M, int lpr) { return cdiv(M, 256 / lpr); }
 
 extern "C" {
 
@@ -633,7 +637,7 @@ int lotus_layernorm_fwd(const act_t* x, const act_t* res, const float* gamma, co
   LOTUS_CHECK_ARG(x && gamma && beta && y && M >= 0, "lotus_layernorm_fwd: bad arguments");
   LOTUS_CHECK_ARG(ln_geometry(C, &p.LPR, &p.NV) == 0, "lotus_layernorm_fwd: unsupported C=%d", C);
   if (M == 0) return LOTUS_OK;
-  LOTUS_LAUNCH(ln_fwd_kernel, dim3(cdiv(M, 256 / p.LPR)), dim3(256), 0, (hipStream_t)stream, p);
+  LOTUS_LAUNCH(ln_fwd_kernel, dim3(ln_fwd_grid(M, p.LPR)), dim3(256), 0, (hipStream_t)stream, p);
   LOTUS_LAUNCH_CHECK("lotus_layernorm_fwd");
   return LOTUS_OK;
 }
@@ -643,7 +647,7 @@ static int ln_bwd_grid(int M, int rpb) {
   int grid = cdiv(M > 0 ? M : 1, rpb * 2);  // >= 2 row groups per block, <= 4 blocks per CU
   return grid > LN_BWD_MAX_GRID ? LN_BWD_MAX_GRID : grid;
 }
-size_t lotus_layernorm_bwd_workspace(int M, int C) { return (size_t)LN_BWD_MAX_GRID * 2 * C * sizeof(float); }
+size_t lotus_layernorm_bwd_workspace(int M, int C) { return C > 0 ? (size_t)LN_BWD_MAX_GRID * 2 * C * sizeof(float) : 0; }
 
 // dx = LN'(dy) (+ add); dgamma/dbeta (+)= column sums.  With dgamma == NULL only dx is produced and the
 // per-block column partials stay in `workspace` for lotus_layernorm_bwd_params (which a caller may run on
@@ -704,12 +708,12 @@ int lotus_layernorm_bwd_params_n(const void* workspace, int nparts, int C, float
   return LOTUS_OK;
 }
 
-size_t lotus_batchnorm_workspace(int M, int C) { return (size_t)BN_MAX_GRID * 2 * C * sizeof(double); }
+size_t lotus_batchnorm_workspace(int M, int C) { return C > 0 ? (size_t)BN_MAX_GRID * 2 * C * sizeof(double) : 0; }
 
 // Forward statistics: sums[2*C+1] (double) = (sum x, sum x^2, M) over the M local rows.
 int lotus_batchnorm_stats(const act_t* x, double* sums, int M, int C, void* workspace, size_t workspace_bytes,
                           void* stream) {
-  LOTUS_CHECK_ARG(x && sums && C % 4 == 0 && M >= 0, "lotus_batchnorm_stats: bad arguments (C=%d)", C);
+  LOTUS_CHECK_ARG(x && sums && C > 0 && C % 4 == 0 && M >= 0, "lotus_batchnorm_stats: bad arguments (C=%d)", C);
   const int grid = bn_grid(M, C);
   LOTUS_CHECK_ARG(workspace && workspace_bytes >= (size_t)grid * 2 * C * sizeof(double),
                   "lotus_batchnorm_stats: workspace too small");
@@ -730,7 +734,7 @@ int lotus_batchnorm_stats_fused(const act_t* x, double* sums, float* mean, float
                                 int M, int C, float eps, float momentum, void* workspace, size_t workspace_bytes, void* counter,
                                 void* stream) {
   // (mean == invstd == null: the sums alone — the SyncBatchNorm forward, whose statistics are finished after the message)
-  LOTUS_CHECK_ARG(x && sums && (!mean == !invstd) && counter && C % 4 == 0 && M > 0, "lotus_batchnorm_stats_fused: bad arguments (C=%d)", C);
+  LOTUS_CHECK_ARG(x && sums && (!mean == !invstd) && counter && C > 0 && C % 4 == 0 && M > 0, "lotus_batchnorm_stats_fused: bad arguments (C=%d)", C);
   const int grid = bn_grid_fused(M, C);
   LOTUS_CHECK_ARG(workspace && workspace_bytes >= (size_t)(grid + BN_COUNTERS) * 2 * C * sizeof(double), "lotus_batchnorm_stats_fused: workspace too small");
   BnStatP p;
@@ -752,7 +756,7 @@ int lotus_batchnorm_bwd_stats_fused_params(const act_t* dy, const act_t* x, cons
 int lotus_batchnorm_bwd_stats_fused(const act_t* dy, const act_t* x, const float* mean, const float* invstd, const float* gamma,
                                     const float* beta, double* sums, int M, int C, int act, void* workspace, size_t workspace_bytes,
                                     void* counter, void* stream) {
-  LOTUS_CHECK_ARG(dy && x && sums && counter && C % 4 == 0 && M > 0, "lotus_batchnorm_bwd_stats_fused: bad arguments");
+  LOTUS_CHECK_ARG(dy && x && sums && counter && C > 0 && C % 4 == 0 && M > 0, "lotus_batchnorm_bwd_stats_fused: bad arguments");
   const int grid = bn_grid_fused(M, C);
   LOTUS_CHECK_ARG(workspace && workspace_bytes >= (size_t)(grid + BN_COUNTERS) * 2 * C * sizeof(double), "lotus_batchnorm_bwd_stats_fused: workspace too small");
   BnStatP p;
@@ -768,7 +772,7 @@ int lotus_batchnorm_bwd_stats_fused(const act_t* dy, const act_t* x, const float
 int lotus_batchnorm_bwd_stats_fused_params(const act_t* dy, const act_t* x, const float* mean, const float* invstd, const float* gamma,
                                            const float* beta, double* sums, float* dgamma, float* dbeta, int M, int C, int act,
                                            void* workspace, size_t workspace_bytes, void* counter, void* stream) {
-  LOTUS_CHECK_ARG(dy && x && sums && dgamma && dbeta && counter && C % 4 == 0 && M > 0, "lotus_batchnorm_bwd_stats_fused_params: bad arguments");
+  LOTUS_CHECK_ARG(dy && x && sums && dgamma && dbeta && counter && C > 0 && C % 4 == 0 && M > 0, "lotus_batchnorm_bwd_stats_fused_params: bad arguments");
   const int grid = bn_grid_fused(M, C);
   LOTUS_CHECK_ARG(workspace && workspace_bytes >= (size_t)(grid + BN_COUNTERS) * 2 * C * sizeof(double), "lotus_batchnorm_bwd_stats_fused_params: workspace too small");
   BnStatP p;
@@ -784,7 +788,7 @@ int lotus_batchnorm_bwd_stats_fused_params(const act_t* dy, const act_t* x, cons
 // mean/invstd from (possibly all-reduced) sums[2*C+1]; updates running stats if given.
 int lotus_batchnorm_finalize(const double* sums, float* mean, float* invstd, float* running_mean,
                              float* running_var, int C, float eps, float momentum, void* stream) {
-  LOTUS_CHECK_ARG(sums && mean && invstd, "lotus_batchnorm_finalize: bad arguments");
+  LOTUS_CHECK_ARG(sums && mean && invstd && C > 0, "lotus_batchnorm_finalize: bad arguments");
   LOTUS_LAUNCH(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, sums, mean,
                      invstd, running_mean, running_var, C, eps, momentum);
   LOTUS_LAUNCH_CHECK("lotus_batchnorm_finalize");
@@ -793,6 +797,7 @@ int lotus_batchnorm_finalize(const double* sums, float* mean, float* invstd, flo
 
 int lotus_batchnorm_eval_stats(const float* running_mean, const float* running_var, float* mean, float* invstd, int C,
                                float eps, void* stream) {
+  LOTUS_CHECK_ARG(running_mean && running_var && mean && invstd && C > 0, "lotus_batchnorm_eval_stats: bad arguments");
   LOTUS_LAUNCH(bn_eval_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, running_mean,
                      running_var, mean, invstd, C, eps);
   LOTUS_LAUNCH_CHECK("lotus_batchnorm_eval_stats");
@@ -802,7 +807,7 @@ int lotus_batchnorm_eval_stats(const float* running_mean, const float* running_v
 // y = act((x - mean) * invstd * gamma + beta)
 int lotus_batchnorm_apply(const act_t* x, const float* mean, const float* invstd, const float* gamma,
                           const float* beta, act_t* y, int M, int C, int act, void* stream) {
-  LOTUS_CHECK_ARG(x && y && C % 4 == 0, "lotus_batchnorm_apply: bad arguments");
+  LOTUS_CHECK_ARG(x && y && C > 0 && C % 4 == 0, "lotus_batchnorm_apply: bad arguments");
   if (M == 0) return LOTUS_OK;
   BnApplyP p;
   memset(&p, 0, sizeof(p));
@@ -820,7 +825,7 @@ int lotus_batchnorm_apply(const act_t* x, const float* mean, const float* invstd
 int lotus_batchnorm_apply_sums(const act_t* x, const double* sums, const float* gamma, const float* beta, act_t* y, float* mean,
                                float* invstd, float* running_mean, float* running_var, int M, int C, int act, float eps,
                                float momentum, void* stream) {
-  LOTUS_CHECK_ARG(sums && mean && invstd && C % 4 == 0 && (M == 0 || (x && y)), "lotus_batchnorm_apply_sums: bad arguments");
+  LOTUS_CHECK_ARG(sums && mean && invstd && C > 0 && C % 4 == 0 && (M == 0 || (x && y)), "lotus_batchnorm_apply_sums: bad arguments");
   BnApplyP p;
   memset(&p, 0, sizeof(p));
   p.x = x; p.gamma = gamma; p.beta = beta; p.y = y;
@@ -840,7 +845,7 @@ int lotus_batchnorm_apply_sums(const act_t* x, const double* sums, const float* 
 int lotus_batchnorm_bwd_stats(const act_t* dy, const act_t* x, const float* mean, const float* invstd,
                               const float* gamma, const float* beta, double* sums, int M, int C, int act,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  LOTUS_CHECK_ARG(dy && x && sums && C % 4 == 0, "lotus_batchnorm_bwd_stats: bad arguments");
+  LOTUS_CHECK_ARG(dy && x && sums && C > 0 && C % 4 == 0, "lotus_batchnorm_bwd_stats: bad arguments");
   const int grid = bn_grid(M, C);
   LOTUS_CHECK_ARG(workspace && workspace_bytes >= (size_t)grid * 2 * C * sizeof(double),
                   "lotus_batchnorm_bwd_stats: workspace too small");
@@ -860,7 +865,7 @@ int lotus_batchnorm_bwd_stats(const act_t* dy, const act_t* x, const float* mean
 int lotus_batchnorm_bwd_apply(const act_t* dy, const act_t* x, const float* mean, const float* invstd,
                               const float* gamma, const float* beta, const double* sums, act_t* dx, float* dgamma,
                               float* dbeta, int M, int C, int act, int train, int accumulate, void* stream) {
-  LOTUS_CHECK_ARG(dy && x && dx && sums && C % 4 == 0, "lotus_batchnorm_bwd_apply: bad arguments");
+  LOTUS_CHECK_ARG(dy && x && dx && sums && C > 0 && C % 4 == 0, "lotus_batchnorm_bwd_apply: bad arguments");
   BnApplyP p;
   memset(&p, 0, sizeof(p));
   p.x = x; p.dy = dy; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta;
@@ -881,6 +886,37 @@ int lotus_batchnorm_bwd_apply(const act_t* dy, const act_t* x, const float* mean
     LOTUS_LAUNCH(bn_apply_kernel, dim3(grid), dim3(256), 0, st, p);
   }
   LOTUS_LAUNCH_CHECK("lotus_batchnorm_bwd_apply");
+  return LOTUS_OK;
+}
+
+// The launch plan of the kernels above for (M, C), from the helpers the launches themselves use (tests pin the branch a shape
+// lands in with it).  kind 0 LayerNorm forward: out[4] = {lanes per row, quads per lane, rows per block, grid}; 1 LayerNorm
+// backward: out[5] = {lanes per row, quads per lane, rows per block, grid (= partial rows), passes of the row loop}; 2 / 3
+// BatchNorm statistics in two launches / fused: out[7] = {row slots per block, threads per row, column slabs, grid, groups of the
+// last-arrival reduction (0 for kind 2), rows every row slot walks, row slots that walk one more}; 4 BatchNorm apply: out[3] =
+// {grid, blocks per column period, 1 when the 4096-block cap was hit}.
+int lotus_norm_plan(int kind, int M, int C, int* out) {
+  LOTUS_CHECK_ARG(out && M >= 0 && C > 0 && kind >= 0 && kind <= 4, "lotus_norm_plan: bad arguments (kind=%d, C=%d)", kind, C);
+  if (kind <= 1) {
+    int lpr, nv;
+    LOTUS_CHECK_ARG((kind ? ln_geometry_bwd(C, &lpr, &nv) : ln_geometry(C, &lpr, &nv)) == 0, "lotus_norm_plan: unsupported C=%d", C);
+    const int rpb = 256 / lpr;
+    out[0] = lpr; out[1] = nv; out[2] = rpb;
+    out[3] = kind ? ln_bwd_grid(M, rpb) : ln_fwd_grid(M, lpr);
+    if (kind) out[4] = cdiv(M, (long)out[3] * rpb);
+    return LOTUS_OK;
+  }
+  LOTUS_CHECK_ARG(C % 4 == 0, "lotus_norm_plan: unsupported C=%d", C);
+  if (kind == 4) {
+    out[0] = bn_apply_grid((long)M * C / 4, C, out + 1, out + 2);
+    return LOTUS_OK;
+  }
+  const int c4 = C / 4, tpr = bn_tpr(c4);
+  out[0] = bn_rslots(c4); out[1] = tpr; out[2] = cdiv(c4, tpr);
+  out[3] = kind == 3 ? bn_grid_fused(M, C) : bn_grid(M, C);
+  out[4] = kind == 3 ? cdiv(out[3], BN_GS) : 0;
+  const long stride = (long)out[3] * out[0];
+  out[5] = (int)(M / stride); out[6] = (int)(M % stride);
   return LOTUS_OK;
 }
 
