@@ -660,7 +660,7 @@ extern "C" {
 
 int lotus_pool_max_fwd(const act_t* x, const int* members, const int* seg, int nc, int C, act_t* y, int* arg,
                        void* stream) {
-  LOTUS_CHECK_ARG(x && members && seg && y && arg && C % 4 == 0, "lotus_pool_max_fwd: bad arguments");
+  LOTUS_CHECK_ARG(x && members && seg && y && arg && C > 0 && C % 4 == 0, "lotus_pool_max_fwd: bad arguments");
   if (nc == 0) return LOTUS_OK;
   LOTUS_LAUNCH(pool_max_fwd_kernel, dim3(cdiv((long)nc * C / 4, 256)), dim3(256), 0, (hipStream_t)stream, x,
                      members, seg, nc, C, y, arg);
@@ -668,7 +668,7 @@ int lotus_pool_max_fwd(const act_t* x, const int* members, const int* seg, int n
   return LOTUS_OK;
 }
 int lotus_pool_max_bwd(const act_t* dy, const int* arg, const int* cluster, int n, int C, act_t* dx, void* stream) {
-  LOTUS_CHECK_ARG(dy && arg && cluster && dx && C % 4 == 0, "lotus_pool_max_bwd: bad arguments");
+  LOTUS_CHECK_ARG(dy && arg && cluster && dx && C > 0 && C % 4 == 0, "lotus_pool_max_bwd: bad arguments");
   if (n == 0) return LOTUS_OK;
   LOTUS_LAUNCH(pool_max_bwd_kernel, dim3(cdiv((long)n * C / 4, 256)), dim3(256), 0, (hipStream_t)stream, dy, arg,
                      cluster, n, C, dx);
@@ -676,7 +676,7 @@ int lotus_pool_max_bwd(const act_t* dy, const int* arg, const int* cluster, int 
   return LOTUS_OK;
 }
 int lotus_unpool_fwd(const act_t* skip, const act_t* up, const int* cluster, int n, int C, act_t* x, void* stream) {
-  LOTUS_CHECK_ARG(skip && up && cluster && x && C % 4 == 0, "lotus_unpool_fwd: bad arguments");
+  LOTUS_CHECK_ARG(skip && up && cluster && x && C > 0 && C % 4 == 0, "lotus_unpool_fwd: bad arguments");
   if (n == 0) return LOTUS_OK;
   LOTUS_LAUNCH(unpool_fwd_kernel, dim3(cdiv((long)n * C / 4, 256)), dim3(256), 0, (hipStream_t)stream, skip, up,
                      cluster, n, C, x);
@@ -684,7 +684,7 @@ int lotus_unpool_fwd(const act_t* skip, const act_t* up, const int* cluster, int
   return LOTUS_OK;
 }
 int lotus_unpool_bwd(const act_t* dx, const int* members, const int* seg, int nc, int C, act_t* dup, void* stream) {
-  LOTUS_CHECK_ARG(dx && members && seg && dup && C % 4 == 0, "lotus_unpool_bwd: bad arguments");
+  LOTUS_CHECK_ARG(dx && members && seg && dup && C > 0 && C % 4 == 0, "lotus_unpool_bwd: bad arguments");
   if (nc == 0) return LOTUS_OK;
   LOTUS_LAUNCH(unpool_bwd_kernel, dim3(cdiv((long)nc * C / 4, 256)), dim3(256), 0, (hipStream_t)stream, dx,
                      members, seg, nc, C, dup);
@@ -709,7 +709,7 @@ int lotus_cloud_max_fwd(const act_t* x, const int* off, int B, int C, act_t* y, 
 }
 int lotus_cloud_max_bwd(const act_t* dy, const int* arg, const int* batch, int n, int C, const act_t* add, act_t* dx,
                         void* stream) {
-  LOTUS_CHECK_ARG(dy && arg && batch && dx && C % 4 == 0, "lotus_cloud_max_bwd: bad arguments");
+  LOTUS_CHECK_ARG(dy && arg && batch && dx && C > 0 && C % 4 == 0, "lotus_cloud_max_bwd: bad arguments");
   if (n == 0) return LOTUS_OK;
   LOTUS_LAUNCH(cloud_max_bwd_kernel, dim3(cdiv((long)n * C / 4, 256)), dim3(256), 0, (hipStream_t)stream, dy, arg,
                      batch, n, C, add, dx);
@@ -725,7 +725,7 @@ size_t lotus_loss_stats_floats(int B) { return (size_t)B * 3 * (4 + POS_CE_PART 
 int lotus_loss_fwd(const act_t* xt, const act_t* ae, const float* tgt, const float* gt, const int* off, int B, int nb,
                    int nrot, int ga, float pos_w, float rot_w, float* losses, float* pos_stats, float* dae,
                    void* stream) {
-  LOTUS_CHECK_ARG(xt && ae && tgt && gt && off && losses && pos_stats && B > 0, "lotus_loss_fwd: bad arguments");
+  LOTUS_CHECK_ARG(xt && ae && tgt && gt && off && losses && pos_stats && B > 0 && nb > 0 && nrot > 0 && ga >= 7, "lotus_loss_fwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   float* part = pos_stats + (size_t)B * 3 * 4;  // slice partials live behind the per-(cloud, axis) stats
   LOTUS_LAUNCH(pos_ce_part_kernel, dim3(POS_CE_SPLITS, B * 3), dim3(256), 0, st, xt, tgt, off, nb, part);
@@ -738,7 +738,7 @@ int lotus_loss_fwd(const act_t* xt, const act_t* ae, const float* tgt, const flo
 int lotus_loss_bwd(const act_t* xt, const float* tgt, const int* off, const int* batch, const float* pos_stats,
                    const float* dae_saved, const float* gl, float pos_w, float rot_w, int B, int n, int nb, int nrot,
                    act_t* dxt, act_t* dae_out, void* stream) {
-  LOTUS_CHECK_ARG(xt && tgt && off && batch && pos_stats && dae_saved && gl && dxt && dae_out, "lotus_loss_bwd: bad arguments");
+  LOTUS_CHECK_ARG(xt && tgt && off && batch && pos_stats && dae_saved && gl && dxt && dae_out && nb > 0 && nrot > 0, "lotus_loss_bwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   const long total = (long)n * 3 * nb;
   LOTUS_LAUNCH(pos_ce_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, xt, tgt, off, batch, pos_stats, gl,
@@ -762,7 +762,7 @@ int lotus_pos_ce_fwd(const act_t* xt, const float* tgt, const int* off, int B, i
 }
 int lotus_pos_ce_bwd(const act_t* xt, const float* tgt, const int* off, const int* batch, const float* pos_stats,
                      const float* g, int B, int n, int nb, act_t* dxt, void* stream) {
-  LOTUS_CHECK_ARG(xt && tgt && off && batch && pos_stats && g && dxt && B > 0, "lotus_pos_ce_bwd: bad arguments");
+  LOTUS_CHECK_ARG(xt && tgt && off && batch && pos_stats && g && dxt && B > 0 && nb > 0, "lotus_pos_ce_bwd: bad arguments");
   if (n == 0) return LOTUS_OK;
   const long total = (long)n * 3 * nb;
   LOTUS_LAUNCH(pos_ce_bwd_w_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, xt, tgt, off, batch,
@@ -783,7 +783,7 @@ int lotus_mp_loss_fwd(const act_t* ae, const float* gt, const float* stop, const
 }
 int lotus_mp_loss_bwd(const float* dae, const float* dce, const float* g, float pos_w, float rot_w, int B, int T, int nrot,
                       act_t* dae_out, float* dce_out, void* stream) {
-  LOTUS_CHECK_ARG(dae && dce && g && dae_out && dce_out && B > 0 && T > 0 && nrot > 0, "lotus_mp_loss_bwd: bad arguments");
+  LOTUS_CHECK_ARG(dae && dce && g && dae_out && dce_out && B > 0 && T > 0 && nrot > 0 && B <= 8192, "lotus_mp_loss_bwd: bad arguments");
   const int W = nrot * 3 + 2;
   const long nae = (long)B * T * W, nce = (long)B * T * 3;
   LOTUS_LAUNCH(mp_loss_bwd_kernel, dim3(cdiv(nae, 256)), dim3(256), 0, (hipStream_t)stream, dae, dce, g, pos_w, rot_w, W, nae, nce,
