@@ -311,7 +311,11 @@ int lotus_norm_plan(int kind, int M, int C, int* out);
  * null) and 0 < k_max <= 32 — the point <-> instruction cross attention, whose key side is a cloud's 6-19 tokens — the call
  * takes the short-key kernels (one lane per query, keys / values as LDS broadcast rows, exact fp32 whatever `precision`).
  * k_max is a HARD contract: every tile's k_len must be <= k_max.  The backward kernel of that family keeps per-query state in
- * registers across a tile's key chunks and traps (GPU fault, loud) on a block that walks several tiles with k_len > 32. */
+ * registers across a tile's key chunks and traps (GPU fault, loud) on a block that walks several tiles with k_len > 32.
+ * qn_w, qn_b, kn_w, kn_b ALL null: attention without q/k normalisation (qk_norm False, model.py:393-394: nn.Identity) — the q
+ * and k rows enter the score product as loaded.  Built for precision 0 with fp32 storage only: another precision, or the
+ * lotus_b16_ twin, returns LOTUS_E_ARG and says so; some but not all of the four null is LOTUS_E_ARG too.  Such a call always
+ * takes the 128 x 128 tile kernels, whatever k_max and LOTUS_XQ say. */
 int lotus_attention_fwd(const lotus_act_t* q, long q_ld, int q_off, const lotus_act_t* kv, long kv_ld, int k_off, int v_off,
                         const int* qidx, const int* kidx, const int* owner, const int* tiles, int ntiles,
                         const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b, lotus_act_t* out,
@@ -320,7 +324,10 @@ int lotus_attention_fwd(const lotus_act_t* q, long q_ld, int q_off, const lotus_
 size_t lotus_attention_bwd_workspace(int nblocks, int H);
 /* blocks: int32 [nblocks][6] = first_tile, n_tiles, tile_step, part_slot, k_start, k_len.  kext / ext_pos /
  * dkv_extra (optional, from lotus_fe_patch): k/v gradients of the borrowed tail-patch copies go to a side
- * buffer [n_extra][2*H*d] and are added to their point afterwards (no atomics, no zero-fill of dkv). */
+ * buffer [n_extra][2*H*d] and are added to their point afterwards (no atomics, no zero-fill of dkv).
+ * qn_w, qn_b, kn_w, kn_b ALL null: backward of the attention without q/k normalisation (rules as at lotus_attention_fwd).
+ * dq / dk are then the plain products; dqn_w, dqn_b, dkn_w, dkn_b are not written and may be null, and no workspace is
+ * used (workspace null / workspace_bytes 0 are fine). */
 int lotus_attention_bwd(const lotus_act_t* q, long q_ld, int q_off, const lotus_act_t* kv, long kv_ld, int k_off, int v_off,
                         const int* qidx, const int* kidx, const int* owner, const int* tiles, const int* blocks,
                         int nblocks, const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b,

@@ -256,8 +256,10 @@ class AdaSelfAttnFn(torch.autograd.Function):
 
     @_fwd
     def forward(ctx, x, mod, g, b, wqkv, bqkv, qnw, qnb, knw, knb, wp, bp, lvl, H, drop_p, seed, attn_p, dpath, bank, j):
+        """qnw = qnb = knw = knb = None: a block without q_norm / k_norm (qk_norm False)."""
         n, mean, rstd = adaln_fwd(x, g, b, mod, lvl)
-        y, qkv, att, lse = ops.selfattn_branch_fwd(n, x, wqkv, bqkv, (qnw, qnb), (knw, knb), wp, bp, lvl, H, drop_p, seed, attn_p, dpath)
+        qn, kn = ((qnw, qnb), (knw, knb)) if qnw is not None else (None, None)
+        y, qkv, att, lse = ops.selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, attn_p, dpath)
         ctx.meta = (lvl, H, drop_p, seed, attn_p, float(dpath), bank, j)
         ctx.save_for_backward(x, g, b, mod, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd)
         return y
@@ -267,7 +269,8 @@ class AdaSelfAttnFn(torch.autograd.Function):
         x, g, b, mod, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd = ctx.saved_tensors
         lvl, H, p, seed, attn_p, dpath, bank, j = ctx.meta
         dy = dy.contiguous()
-        dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp = ops.selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, (qnw, qnb), (knw, knb), wp,
+        qn, kn = ((qnw, qnb), (knw, knb)) if qnw is not None else (None, None)
+        dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp = ops.selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, qn, kn, wp,
                                                                              lvl, H, p, seed, attn_p, dpath, None)
         dmod = bank.grad_slice(j)
         dx, dg, db = adaln_bwd(dn, x, mean, rstd, g, b, mod, dmod, lvl, add=dy)
@@ -408,14 +411,15 @@ def _pd_bn(c, ctx):
 
 
 class AdaBlock(nn.Module):
-    """model.py:586-680 with PDNorm LayerNorms (cpe.2, norm1, norm2); attn.q_norm / k_norm stay plain."""
+    """model.py:586-680 with PDNorm LayerNorms (cpe.2, norm1, norm2); attn.q_norm / k_norm stay plain (nn.Identity when
+    qk_norm is False: the patch attention then runs without them)."""
 
-    def __init__(self, c, h, mlp_ratio, ctx):
+    def __init__(self, c, h, mlp_ratio, ctx, qk_norm=True):
         super().__init__()
         self.num_heads = h
         self.cpe = nn.Sequential(SubMConv3d(c, c, 3, bias=True), nn.Linear(c, c), _pd_ln(c, ctx))
         self.norm1 = nn.Sequential(_pd_ln(c, ctx))
-        self.attn = _Attn(c, h)
+        self.attn = _Attn(c, h, qk_norm)
         self.norm2 = nn.Sequential(_pd_ln(c, ctx))
         self.mlp = nn.Sequential(_MLP(c, int(c * mlp_ratio)))
 
@@ -465,6 +469,7 @@ class PointTransformerV3AdaNorm(PointTransformerV3CA):
     forward prologue and the encoder / decoder walk, the front end, its prefetch, seeds and pack helpers are
     PointTransformerV3CA's; this class supplies the PDNorm modules and the steps of a pass that run them."""
     block_cls = AdaBlock
+    plain_attention = True
 
     def __init__(self, *args, pdnorm_bn=True, pdnorm_ln=True, pdnorm_decouple=False, pdnorm_adaptive=True, **kw):
         super().__init__(*args, pdnorm_bn=pdnorm_bn, pdnorm_ln=pdnorm_ln, pdnorm_decouple=pdnorm_decouple,
@@ -490,7 +495,7 @@ class PointTransformerV3AdaNorm(PointTransformerV3CA):
         return _AdaUp(cin, cskip, cout, self.context_channels)
 
     def _add_depth(self, stage, i, c, h, mlp_ratio):
-        stage.add_module(f"block{i}", AdaBlock(c, h, mlp_ratio, self.context_channels))
+        stage.add_module(f"block{i}", AdaBlock(c, h, mlp_ratio, self.context_channels, self.qk_norm))
 
     def _index_sites(self):
         self._pdnorms = [m for m in self.modules() if isinstance(m, PDNorm)]  # slice j of the modulation bank = norm j
@@ -564,9 +569,9 @@ class PointTransformerV3AdaNorm(PointTransformerV3CA):
         x = AdaCpeFn.apply(x, xs, mods[pid[id(pc)]], c0.weight, c0.bias, c1.weight, c1.bias, pc.norm.weight, pc.norm.bias,
                            lvl_o, fw.packs[blk], bank, pid[id(pc)])
         a, n1 = blk.attn, blk.norm1[0]
-        x = AdaSelfAttnFn.apply(x, mods[pid[id(n1)]], n1.norm.weight, n1.norm.bias, a.qkv.weight, a.qkv.bias, a.q_norm.weight,
-                                a.q_norm.bias, a.k_norm.weight, a.k_norm.bias, a.proj.weight, a.proj.bias, lvl_o, blk.num_heads,
-                                p, si, fw.pa, dpath, bank, pid[id(n1)])
+        qk = (a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias) if self.qk_norm else (None,) * 4
+        x = AdaSelfAttnFn.apply(x, mods[pid[id(n1)]], n1.norm.weight, n1.norm.bias, a.qkv.weight, a.qkv.bias, *qk,
+                                a.proj.weight, a.proj.bias, lvl_o, blk.num_heads, p, si, fw.pa, dpath, bank, pid[id(n1)])
         m, n2 = blk.mlp[0], blk.norm2[0]
         return AdaFfnFn.apply(x, mods[pid[id(n2)]], n2.norm.weight, n2.norm.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight,
                               m.fc2.bias, lvl_o, p, mix_seed(si, 2), dpath, bank, pid[id(n2)])

@@ -165,6 +165,10 @@ ADANORM_SWITCHES = ["model_class", "SimplePolicyPTV3AdaNorm", "ptv3_config.pdnor
                     "ptv3_config.pdnorm_affine", "True", "ptv3_config.pdnorm_only_decoder", "False"]
 ADANORM_OVERRIDES = {"adanorm_v1": V1_OVERRIDES + ADANORM_SWITCHES, "adanorm_tiny": TINY_OVERRIDES + ADANORM_SWITCHES,
                      "adanorm_tinyctx": TINYCTX_OVERRIDES + ADANORM_SWITCHES}
+# ... with the YAML's own qk_norm False (attention without q/k LayerNorm); 'adanorm_yaml' is the YAML as shipped, no override
+PLAIN_ATTN = ["ptv3_config.qk_norm", "False"]
+ADANORM_OVERRIDES.update({"adanorm_yaml": [], "adanorm_tiny_plain": ADANORM_OVERRIDES["adanorm_tiny"] + PLAIN_ATTN,
+                          "adanorm_v1_plain": ADANORM_OVERRIDES["adanorm_v1"] + PLAIN_ATTN})
 
 
 # The regression head of the YAML's own defaults (simple_policy_ptv3.yaml: pos_pred_type 'heatmap_mlp', rot_pred_type 'euler')
@@ -178,6 +182,8 @@ def preset(name="v1"):
     """'v1' / 'tiny': 3D-LOTUS policy; 'peract': the RLBench-18task (PerAct) variant of BASELINE configs[4] (same network;
     its bf16 compute mode is ops.set_gemm_precision("bf16")); 'mp' / 'mp_tiny': 3D-LOTUS++ motion planner (configs[3]);
     'adanorm_v1' / 'adanorm_tiny' / 'adanorm_tinyctx': the policy networks as SimplePolicyPTV3AdaNorm (adaptive PDNorm);
+    'adanorm_yaml': simple_policy_ptv3.yaml as shipped (= load_model_config(None)); 'adanorm_tiny_plain' / 'adanorm_v1_plain':
+    adanorm_tiny / adanorm_v1 with qk_norm False;
     'tiny_reg' / 'v1_reg' / 'adanorm_tiny_reg': their base preset with the regression head (heatmap_mlp positions, euler)."""
     if name in ("mp", "mp_tiny", "mp_tinyctx"):
         model = copy.deepcopy(_YAML_MODEL)

@@ -222,8 +222,11 @@ __device__ __forceinline__ f32x16 mfma_split(const uint4& ah, const uint4& al, c
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(abf16x8, ah), __builtin_bit_cast(abf16x8, bh), acc, 0, 0, 0);
 }
 
-template <int PREC>
+// NORM = false (exact fp32 only): attention without q_norm / k_norm — the q and k rows enter the score product as loaded: no
+// affine vectors, no ln_rows pass and one barrier less; everything after the score product is the same code.
+template <int PREC, bool NORM = true>
 __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnP p) {
+  static_assert(NORM || PREC == 0, "the no-norm variant exists in exact fp32 only");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   AttnSmem s = carve(smem, false);
   const int tid = threadIdx.x, wave = tid >> 6, l31 = tid & 31, hh = (tid >> 5) & 1;
@@ -236,7 +239,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnP p) {
     s.krow[tid] = tid < k_len ? (p.kidx ? p.kidx[k_start + tid] : k_start + tid) : -1;
     s.qown[tid] = tid < q_len ? (p.owner ? p.owner[q_start + tid] : 1) : 0;
   }
-  load_affine(p, s);
+  if constexpr (NORM) load_affine(p, s);
   __syncthreads();
   {
     const RowSrc src[3] = {{s.Q, p.q, p.q_ld, p.q_off + h * d, s.qrow, q_len}, {s.K, p.kv, p.kv_ld, p.k_off + h * d, s.krow, k_len},
@@ -244,9 +247,11 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnP p) {
     load_rows_batch<3>(src, d);
   }
   __syncthreads();
-  if (tid < AT) ln_rows<true>(s.Q, s.qrstd, tid, q_len, d, p.eps, s.gq, s.bq);
-  else ln_rows<true>(s.K, s.krstd, tid - AT, k_len, d, p.eps, s.gk, s.bk);
-  __syncthreads();
+  if constexpr (NORM) {
+    if (tid < AT) ln_rows<true>(s.Q, s.qrstd, tid, q_len, d, p.eps, s.gq, s.bq);
+    else ln_rows<true>(s.K, s.krstd, tid - AT, k_len, d, p.eps, s.gk, s.bk);
+    __syncthreads();
+  }
 
   const int r0 = wave * 32;
   if (r0 >= q_len) return;
@@ -820,11 +825,15 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int xswz(int key) { return ((key & 1) << 2) | ((key >> 1) & 3); }
 
+// NORM = false: attention without q_norm / k_norm.  The key fragment is k * scale * log2(e), the accumulator starts at 0
+// (-inf for absent keys), dK^T accumulates over the q rows as loaded, the dQ quadrants read the k rows as loaded, and dq / dk
+// leave as the products dS k / dS^T q: no LayerNorm forward or backward, no column passes, no ln_part partials.
+template <bool NORM = true>
 __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(AttnP p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   AttnSmem s = carve(smem, true);
-  __shared__ float lnacc[4][32];
-  __shared__ float colred[2][8][32];
+  __shared__ float lnacc[NORM ? 4 : 1][32];
+  __shared__ float colred[NORM ? 2 : 1][NORM ? 8 : 1][32];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = tid & 31, hh = (tid >> 5) & 1;
   const int h = blockIdx.y, d = p.d;
   const int* bd = p.blocks + blockIdx.x * 6;
@@ -838,18 +847,22 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(AttnP p) {
     s.krow[tid] = tid < k_len ? (p.kidx ? p.kidx[k_start + tid] : k_start + tid) : -1;
     s.kext[tid] = (tid < k_len && p.kext) ? p.kext[k_start + tid] : -1;
   }
-  if (tid < 4 * 32) lnacc[tid >> 5][tid & 31] = 0.f;
-  load_affine(p, s);
+  if constexpr (NORM) {
+    if (tid < 4 * 32) lnacc[tid >> 5][tid & 31] = 0.f;
+    load_affine(p, s);
+  }
   __syncthreads();
   {
     const RowSrc src[2] = {{s.K, p.kv, p.kv_ld, p.k_off + h * d, s.krow, k_len}, {s.V, p.kv, p.kv_ld, p.v_off + h * d, s.krow, k_len}};
     load_rows_batch<2>(src, d);
   }
   __syncthreads();
-  if (tid >= AT) ln_rows<false>(s.K, s.krstd, tid - AT, k_len, d, p.eps, nullptr, nullptr);
-  __syncthreads();
+  if constexpr (NORM) {
+    if (tid >= AT) ln_rows<false>(s.K, s.krstd, tid - AT, k_len, d, p.eps, nullptr, nullptr);
+    __syncthreads();
+  }
 
-  const float gq_l = s.gq[l31], bq_l = s.bq[l31];
+  const float gq_l = NORM ? s.gq[l31] : 1.f, bq_l = NORM ? s.bq[l31] : 0.f;
   const float sl2 = p.scale * 1.4426950408889634f;
   // this wave's keys: hoisted fragments (k = 2 s2 + hh).  q_norm's affine and scale * log2(e) are folded into the key
   // fragment, (xq g + b) . kn = xq . (g kn) + b . kn; the bias term c_a starts the accumulator (-inf for absent keys)
@@ -860,18 +873,26 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(AttnP p) {
 #pragma unroll
     for (int s2 = 0; s2 < 16; ++s2) {
       const int k = 2 * s2 + hh;
-      const float kn = s.K[kj * ALD + k] * s.gk[k] + s.bk[k];
-      c_a += s.bq[k] * kn;
-      kb[s2] = kn * s.gq[k] * sl2;
+      if constexpr (NORM) {
+        const float kn = s.K[kj * ALD + k] * s.gk[k] + s.bk[k];
+        c_a += s.bq[k] * kn;
+        kb[s2] = kn * s.gq[k] * sl2;
+      } else {
+        kb[s2] = s.K[kj * ALD + k] * sl2;
+      }
       vb[s2] = s.V[kj * ALD + k];
     }
-    c_a += __shfl_xor(c_a, 32, 64);
-    c_a = kj < k_len ? c_a * sl2 : -INFINITY;
+    if constexpr (NORM) {
+      c_a += __shfl_xor(c_a, 32, 64);
+      c_a = kj < k_len ? c_a * sl2 : -INFINITY;
+    } else {
+      c_a = kj < k_len ? 0.f : -INFINITY;
+    }
   }
   f32x16 acc_dv = zero16(), acc_dk = zero16();
   // the dQ quadrant of this wave: head columns 16 dh + (lane & 15), queries 16 qh + (lane & 15) of the running query tile
   const int dh = wave & 1, qh = wave >> 1, l15 = lane & 15, kq = lane >> 4;
-  const float gk_c = s.gk[16 * dh + l15], bk_c = s.bk[16 * dh + l15];
+  const float gk_c = NORM ? s.gk[16 * dh + l15] : 1.f, bk_c = NORM ? s.bk[16 * dh + l15] : 0.f;
   __syncthreads();  // every wave holds its V fragment: the V image may become X
 
   for (int ti = 0; ti < n_tiles; ++ti) {
@@ -914,8 +935,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(AttnP p) {
       }
     }
     __syncthreads();
-    if (tid < AT) ln_rows<false>(s.Q, s.qrstd, tid, q_len, d, p.eps, nullptr, nullptr);
-    __syncthreads();
+    if constexpr (NORM) {
+      if (tid < AT) ln_rows<false>(s.Q, s.qrstd, tid, q_len, d, p.eps, nullptr, nullptr);
+      __syncthreads();
+    }
 
     // dropout index ((tile * H + h) * 128 + q) * 128 + key: the (q, key) part only ever touches the low word (keep_lo);
     // x0 = lo * 0x9E3779B1 + s0 advances by a compile-time constant per register
@@ -975,7 +998,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(AttnP p) {
         for (int r = 0; r < 16; ++r) {
           const int qq = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
           acc_dv = __builtin_amdgcn_mfma_f32_32x32x2f32(s.dO[qq * ALD + l31], sa[r], acc_dv, 0, 0, 0);
-          acc_dk = __builtin_amdgcn_mfma_f32_32x32x2f32(s.Q[qq * ALD + l31] * gq_l + bq_l, dpa[r], acc_dk, 0, 0, 0);
+          if constexpr (NORM) acc_dk = __builtin_amdgcn_mfma_f32_32x32x2f32(s.Q[qq * ALD + l31] * gq_l + bq_l, dpa[r], acc_dk, 0, 0, 0);
+          else acc_dk = __builtin_amdgcn_mfma_f32_32x32x2f32(s.Q[qq * ALD + l31], dpa[r], acc_dk, 0, 0, 0);
         }
       }
       __syncthreads();  // (B) X holds dS of every key for this query tile; nobody reads rows qt*32.. of the dO image any more
@@ -988,7 +1012,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(AttnP p) {
 #pragma unroll
           for (int s4 = 0; s4 < 8; ++s4) {
             const int key = 32 * t + 4 * s4 + kq;
-            const float a = kcol[key * ALD] * gk_c + bk_c;
+            const float a = NORM ? kcol[key * ALD] * gk_c + bk_c : kcol[key * ALD];
             const float b = X[key * 32 + ((((ql >> 2) ^ xswz(key)) << 2) | (ql & 3))];
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
           }
@@ -1000,7 +1024,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(AttnP p) {
     __syncthreads();
     // rows of query tiles that were not run (q_len <= 96) still hold dO: they are beyond q_len and never read below
     // q_norm affine gradients (column pass), then LN backward (row pass), then store
-    {  // column sums over the tile's rows with all 256 threads: 8 row slices x 32 columns, then an 8-way tree
+    if constexpr (NORM) {  // column sums over the tile's rows with all 256 threads: 8 row slices x 32 columns, then an 8-way tree
       const int j = tid & 31, part = tid >> 5;
       float ag = 0.f, ab = 0.f;
       if (j < d)
@@ -1012,15 +1036,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(AttnP p) {
       colred[0][part][j] = ag;
       colred[1][part][j] = ab;
     }
-    __syncthreads();
-    if (tid < 64) {
-      const int which = tid >> 5, j = tid & 31;  // 0: dgamma_q, 1: dbeta_q
-      float a = 0.f;
-      for (int k = 0; k < 8; ++k) a += colred[which][k][j];
-      lnacc[which][j] += a;
+    if constexpr (NORM) {
+      __syncthreads();
+      if (tid < 64) {
+        const int which = tid >> 5, j = tid & 31;  // 0: dgamma_q, 1: dbeta_q
+        float a = 0.f;
+        for (int k = 0; k < 8; ++k) a += colred[which][k][j];
+        lnacc[which][j] += a;
+      }
+      if (tid < AT) ln_rows_bwd(s.dO, s.Q, s.qrstd, tid, q_len, d, s.gq);
+      __syncthreads();
     }
-    if (tid < AT) ln_rows_bwd(s.dO, s.Q, s.qrstd, tid, q_len, d, s.gq);
-    __syncthreads();
     store_rows(s.dO, p.dq, p.dq_ld, p.dq_off + h * d, s.qrow, s.qown, q_len, d, 0);  // one owner per row
     __syncthreads();
   }
@@ -1033,7 +1059,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(AttnP p) {
     s.dO[(r0 + l31) * ALD + dc] = (dc < d) ? acc_dk[r] : 0.f;
   }
   __syncthreads();
-  {
+  if constexpr (NORM) {
     const int j = tid & 31, part = tid >> 5;
     float ag = 0.f, ab = 0.f;
     if (j < d)
@@ -1045,21 +1071,24 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(AttnP p) {
     colred[0][part][j] = ag;
     colred[1][part][j] = ab;
   }
-  __syncthreads();
-  if (tid < 64) {
-    const int which = tid >> 5, j = tid & 31;  // 2: dgamma_k, 3: dbeta_k
-    float a = 0.f;
-    for (int k = 0; k < 8; ++k) a += colred[which][k][j];
-    lnacc[2 + which][j] = a;
+  if constexpr (NORM) {
+    __syncthreads();
+    if (tid < 64) {
+      const int which = tid >> 5, j = tid & 31;  // 2: dgamma_k, 3: dbeta_k
+      float a = 0.f;
+      for (int k = 0; k < 8; ++k) a += colred[which][k][j];
+      lnacc[2 + which][j] = a;
+    }
+    if (tid < AT) ln_rows_bwd(s.dO, s.K, s.krstd, tid, k_len, d, s.gk);
+    __syncthreads();
   }
-  if (tid < AT) ln_rows_bwd(s.dO, s.K, s.krstd, tid, k_len, d, s.gk);
-  __syncthreads();
   act_t* dkv = p.dkv + (long)part_slot * p.dkv_part_stride;
   store_rows(s.dO, dkv, p.dkv_ld, p.dk_off + h * d, s.krow, nullptr, k_len, d, p.atomic_out, p.dkv_extra ? s.kext : nullptr,
              p.dkv_extra, p.dkv_extra_ld, h * d);
   store_rows(s.V, dkv, p.dkv_ld, p.dv_off + h * d, s.krow, nullptr, k_len, d, p.atomic_out, p.dkv_extra ? s.kext : nullptr,
              p.dkv_extra, p.dkv_extra_ld, p.dv_off - p.dk_off + h * d);
-  if (tid < 128) p.ln_part[((long)(blockIdx.x * p.H + h) * 4 + (tid >> 5)) * 32 + (tid & 31)] = lnacc[tid >> 5][tid & 31];
+  if constexpr (NORM)
+    if (tid < 128) p.ln_part[((long)(blockIdx.x * p.H + h) * 4 + (tid >> 5)) * 32 + (tid & 31)] = lnacc[tid >> 5][tid & 31];
 }
 
 // out[which][j] (+)= sum_b part[b][which][j]   (which: dgamma_q, dbeta_q, dgamma_k, dbeta_k)
@@ -1938,6 +1967,21 @@ static bool xq_ok(int k_max, int precision, int atomic_out, int d) {
 
 static int check_geom(int H, int d) { return (d % 4 == 0 && d <= 32 && d >= 4 && H > 0) ? 0 : -1; }
 
+// The q/k LayerNorm of a call: all four of qn_w, qn_b, kn_w, kn_b given = with the norm (1); all four null = attention
+// without q/k normalisation (0: the NORM = false tile kernels, exact fp32 with fp32 storage only); anything else is an
+// argument error (-1).
+static int norm_mode(const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b) {
+  const int n = (qn_w != nullptr) + (qn_b != nullptr) + (kn_w != nullptr) + (kn_b != nullptr);
+  return n == 4 ? 1 : n == 0 ? 0 : -1;
+}
+#define LOTUS_CHECK_NO_NORM(name, precision)                                                                                \
+  do {                                                                                                                     \
+    LOTUS_CHECK_ARG(!LOTUS_ACT_IS_BF16, name ": attention without q/k norm (null qn_w, qn_b, kn_w, kn_b) is not built for " \
+                                             "bf16 activation storage");                                                   \
+    LOTUS_CHECK_ARG((precision) == 0, name ": attention without q/k norm (null qn_w, qn_b, kn_w, kn_b) is built for "       \
+                                           "precision 0 (fp32) only, got precision %d", (int)(precision));                 \
+  } while (0)
+
 extern "C" {
 
 // Forward.  tiles: int32 [ntiles][4] (device).  Rows: q row r lives at q + r*q_ld + q_off + h*d;
@@ -1948,6 +1992,9 @@ int lotus_attention_fwd(const act_t* q, long q_ld, int q_off, const act_t* kv, l
                         long out_ld, float* lse, int H, int d, float scale, float eps, float drop_p,
                         unsigned long long drop_seed, int precision, int k_max, void* stream) {
   LOTUS_CHECK_ARG(q && kv && tiles && out && check_geom(H, d) == 0, "lotus_attention_fwd: bad arguments (H=%d d=%d)", H, d);
+  const int norm = norm_mode(qn_w, qn_b, kn_w, kn_b);
+  LOTUS_CHECK_ARG(norm >= 0, "lotus_attention_fwd: bad arguments (qn_w, qn_b, kn_w, kn_b must be all given or all null)");
+  if (!norm) LOTUS_CHECK_NO_NORM("lotus_attention_fwd", precision);
   if (ntiles == 0) return LOTUS_OK;
   AttnP p;
   memset(&p, 0, sizeof(p));
@@ -1956,6 +2003,14 @@ int lotus_attention_fwd(const act_t* q, long q_ld, int q_off, const act_t* kv, l
   p.qn_w = qn_w; p.qn_b = qn_b; p.kn_w = kn_w; p.kn_b = kn_b;
   p.out = out; p.out_ld = out_ld; p.lse = lse; p.H = H; p.d = d; p.scale = scale; p.eps = eps;
   set_attn_drop(p, drop_p, drop_seed);
+  if (!norm) {  // always the tile kernel: the query-per-lane kernels have no variant without the norm
+    const size_t sm = attn_smem_bytes(false);
+    const auto attn_fwd_plain = attn_fwd_kernel<0, false>;  // (one token for the launch macro)
+    { static bool a0 = false; if (!a0) { (void)hipFuncSetAttribute((const void*)attn_fwd_plain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a0 = true; } }
+    LOTUS_LAUNCH(attn_fwd_plain, dim3(ntiles, H), dim3(256), sm, (hipStream_t)stream, p);
+    LOTUS_LAUNCH_CHECK("lotus_attention_fwd(no q/k norm)");
+    return LOTUS_OK;
+  }
   if (xq_ok(k_max, precision, 0, d)) {  // one lane per query, keys as LDS broadcast rows
     if (d == 32 && k_max > 0 && k_max <= 32 && !owner && xq_mode() != 3)  // the cross attention proper: key tile in registers
       LOTUS_LAUNCH(xq2_fwd_kernel<4>, dim3(ntiles, H), dim3(256), 0, (hipStream_t)stream, p);
@@ -1996,7 +2051,11 @@ int lotus_attention_bwd(const act_t* q, long q_ld, int q_off, const act_t* kv, l
                         int precision, int k_max, void* workspace, size_t workspace_bytes, void* stream) {
   LOTUS_CHECK_ARG(q && kv && tiles && blocks && out && dout && lse && dq && dkv && check_geom(H, d) == 0,
                   "lotus_attention_bwd: bad arguments");
-  LOTUS_CHECK_ARG(workspace && workspace_bytes >= lotus_attention_bwd_workspace(nblocks, H),
+  const int norm = norm_mode(qn_w, qn_b, kn_w, kn_b);
+  LOTUS_CHECK_ARG(norm >= 0, "lotus_attention_bwd: bad arguments (qn_w, qn_b, kn_w, kn_b must be all given or all null)");
+  if (!norm) LOTUS_CHECK_NO_NORM("lotus_attention_bwd", precision);
+  LOTUS_CHECK_ARG(!norm || (dqn_w && dqn_b && dkn_w && dkn_b), "lotus_attention_bwd: bad arguments (null norm gradient)");
+  LOTUS_CHECK_ARG(!norm || (workspace && workspace_bytes >= lotus_attention_bwd_workspace(nblocks, H)),
                   "lotus_attention_bwd: workspace too small");
   if (nblocks == 0) return LOTUS_OK;
   AttnP p;
@@ -2017,6 +2076,20 @@ int lotus_attention_bwd(const act_t* q, long q_ld, int q_off, const act_t* kv, l
   const size_t sm = attn_smem_bytes(true);
   const int prec = precision;
   StopEventOnLast stop_ev;
+  if (!norm) {
+    // always the tile kernel (no query-per-lane variant); no norm partials, so no reduction: it or the fix-up is the last launch
+    { static bool a7 = false; if (!a7) { (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a7 = true; } }
+    if (!p.dkv_extra) stop_ev.last();
+    LOTUS_LAUNCH(attn_bwd2_kernel<false>, dim3(nblocks, H), dim3(256), sm, st, p);
+    if (p.dkv_extra) {
+      const int w4 = 2 * H * d / 4;
+      stop_ev.last();
+      LOTUS_LAUNCH(attn_extra_fixup_kernel, dim3(cdiv((long)n_extra * w4, 256)), dim3(256), 0, st, dkv_extra, 2L * H * d,
+                         ext_pos, kidx, n_extra, w4, dkv, dkv_ld, dk_off);
+    }
+    LOTUS_LAUNCH_CHECK("lotus_attention_bwd(no q/k norm)");
+    return LOTUS_OK;
+  }
   if (xq_ok(k_max, precision, atomic_out, d)) {
     // the cross attention proper (head width 32, <= 32 keys, plain rows): keys in registers, queries streamed (xq2_bwd_kernel)
     if (d == 32 && k_max > 0 && k_max <= 32 && !owner && !p.dkv_extra && xq_mode() != 3)
@@ -2031,8 +2104,8 @@ int lotus_attention_bwd(const act_t* q, long q_ld, int q_off, const act_t* kv, l
     { static bool a5 = false; if (!a5) { (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a5 = true; } }
     LOTUS_LAUNCH(attn_bwd_kernel<1>, dim3(nblocks, H), dim3(256), sm, st, p);
   } else {
-    { static bool a6 = false; if (!a6) { (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a6 = true; } }
-    LOTUS_LAUNCH(attn_bwd2_kernel, dim3(nblocks, H), dim3(256), sm, st, p);
+    { static bool a6 = false; if (!a6) { (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a6 = true; } }
+    LOTUS_LAUNCH(attn_bwd2_kernel<true>, dim3(nblocks, H), dim3(256), sm, st, p);
   }
   if (p.dkv_extra) {
     const int w4 = 2 * H * d / 4;

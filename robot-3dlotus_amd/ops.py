@@ -959,8 +959,19 @@ def bn_bwd_pair(a, bb, training, act):
     return _bn_bwd_apply(*a, training, act, sa, ra), _bn_bwd_apply(*bb, training, act, sb, rb)
 
 
+def _qk_norms(qn, kn):
+    """(qn, kn) as two (weight, bias) pairs; None, None -> the null pointers that select the kernels without the norm."""
+    if qn is None and kn is None:
+        return (None, None), (None, None)
+    if qn is None or kn is None:
+        raise ValueError("attention: q_norm and k_norm are given together or not at all")
+    return qn, kn
+
+
 def attention_fwd(q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, ntiles, qn, kn, out, lse, H, d,
                   drop_p=0.0, seed=0, prec=None, k_max=0):
+    """qn / kn = (weight, bias) of q_norm / k_norm, or both None: attention without q/k normalisation (fp32 only)."""
+    qn, kn = _qk_norms(qn, kn)
     call("lotus_attention_fwd", q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, ntiles,
          qn[0], qn[1], kn[0], kn[1], out, out.stride(0), lse, H, d, float(d ** -0.5), 1e-6, float(drop_p), int(seed),
          _pa(prec), int(k_max))
@@ -969,7 +980,16 @@ def attention_fwd(q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, ti
 def attention_bwd(q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, blocks, nblocks, qn, kn, out,
                   dout, lse, dq, dq_ld, dq_off, dkv, dkv_ld, dk_off, dv_off, part_stride, atomic, H, d, drop_p=0.0, seed=0,
                   kext=None, ext_pos=None, n_extra=0, dkv_extra=None, prec=None, k_max=0):
+    """-> the gradients of q_norm / k_norm (weight, bias, weight, bias); four None when qn = kn = None (no q/k norm)."""
     dev = q.device
+    plain = qn is None and kn is None
+    qn, kn = _qk_norms(qn, kn)
+    if plain:  # no norm partials: the entry point takes neither gradient outputs nor a workspace
+        call("lotus_attention_bwd", q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, blocks, nblocks,
+             None, None, None, None, out, dout, out.stride(0), lse, dq, dq_ld, dq_off, dkv, dkv_ld, dk_off, dv_off,
+             part_stride, atomic, kext, ext_pos, n_extra, dkv_extra, None, None, None, None, 0, H, d, float(d ** -0.5), 1e-6,
+             float(drop_p), int(seed), _pa(prec), int(k_max), None, 0)
+        return [None] * 4
     grads = [torch.empty(d, dtype=torch.float32, device=dev) for _ in range(4)]
     ws = _ws(query("lotus_attention_bwd_workspace", nblocks, H), dev)
     call("lotus_attention_bwd", q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, blocks, nblocks,
@@ -1121,7 +1141,8 @@ def cpe_branch_bwd(dl, dy, xs, cw, lw, c, lvl, wt, same):
 
 
 def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, attn_p, dpath):
-    """n = norm(x) -> (y, qkv, att, lse), y = x + DropPath(drop(proj(PatchAttention(qkv(n))))); qn / kn = (weight, bias)."""
+    """n = norm(x) -> (y, qkv, att, lse), y = x + DropPath(drop(proj(PatchAttention(qkv(n))))); qn / kn = (weight, bias), or
+    both None for attention without q/k normalisation."""
     N, C = x.shape
     qkv, _ = linear_fwd(n, wqkv, bqkv)
     att = torch.empty(N, C, dtype=x.dtype, device=x.device)
@@ -1137,7 +1158,8 @@ def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, 
 
 
 def selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, qn, kn, wp, lvl, H, p, seed, attn_p, dpath, hand):
-    """-> (dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp); `hand`: the hand-over that may hold dy pre-masked (or None)."""
+    """-> (dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp); `hand`: the hand-over that may hold dy pre-masked (or None).
+    gq, bq, gk, bk are None when qn = kn = None."""
     N, C = n.shape
     dyb = drop_path(dy, None, dpath, mix_seed(seed, 5)) if dpath > 0.0 else dy
     dz = _masked(dyb, p, seed, hand)

@@ -411,6 +411,11 @@ class SimplePolicyPTV3AdaNorm(SimplePolicyPTV3CA):
     def forward(self, batch, compute_loss=False, **kwargs):
         if self.act_storage == "bf16":
             raise NotImplementedError("SimplePolicyPTV3AdaNorm: act_storage='bf16' is not built (fp32 activations only)")
+        if not self.ptv3_model.qk_norm:
+            mode = self.gemm_precision or ops.get_gemm_precision()
+            if mode != "fp32":  # the patch attention without q/k LayerNorm exists as exact-fp32 kernels only
+                raise NotImplementedError(f"SimplePolicyPTV3AdaNorm with qk_norm=False is built for gemm_precision None / 'fp32' "
+                                          f"only, got {mode!r}")
         return super().forward(batch, compute_loss, **kwargs)
 
 

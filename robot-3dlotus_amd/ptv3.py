@@ -40,12 +40,13 @@ def _bn(c):
 
 
 class _Attn(nn.Module):
-    def __init__(self, c, h):
+    def __init__(self, c, h, qk_norm=True):
         super().__init__()
         self.qkv = nn.Linear(c, 3 * c)
         self.proj = nn.Linear(c, c)
-        self.q_norm = nn.LayerNorm(c // h, eps=1e-6)
-        self.k_norm = nn.LayerNorm(c // h, eps=1e-6)
+        # qk_norm False: nn.Identity, as the reference registers (model.py:393-394) — same module names, no state entries
+        self.q_norm = nn.LayerNorm(c // h, eps=1e-6) if qk_norm else nn.Identity()
+        self.k_norm = nn.LayerNorm(c // h, eps=1e-6) if qk_norm else nn.Identity()
 
 
 class _CrossAttn(nn.Module):
@@ -172,6 +173,7 @@ class PointTransformerV3CA(nn.Module):
     PDNorm flag rule, the module factories, what runs at the top of a pass (stem and bank), pooling, unpooling and "the
     block(s) at depth i of a stage"."""
     block_cls = Block  # the type _blocks / _block_level index
+    plain_attention = False  # whether the class runs qk_norm=False (attention without q/k LayerNorm): the AdaNorm backbone only
 
     def __init__(self, in_channels=6, order=("z", "z-trans", "hilbert", "hilbert-trans"), stride=(2, 2, 2, 2),
                  enc_depths=(2, 2, 2, 6, 2), enc_channels=(32, 64, 128, 256, 512), enc_num_head=(2, 4, 8, 16, 32),
@@ -186,7 +188,7 @@ class PointTransformerV3CA(nn.Module):
         super().__init__()
         pd = self._pdnorm_unsupported(pdnorm_bn, pdnorm_ln, pdnorm_decouple, pdnorm_adaptive, pdnorm_affine, pdnorm_only_decoder)
         unsupported = dict(**pd, enable_rpe=enable_rpe, cls_mode=cls_mode,
-                           scaled_cosine_attn=scaled_cosine_attn, not_flash=not enable_flash, not_qk_norm=not qk_norm,
+                           scaled_cosine_attn=scaled_cosine_attn, not_flash=not enable_flash, not_qk_norm=not qk_norm and not self.plain_attention,
                            not_pre_norm=not pre_norm, no_qkv_bias=not qkv_bias, qk_scale=qk_scale is not None,
                            add_coords=add_coords_in_attn not in (False, "none", None),
                            depth_lt_1=any(d < 1 for d in list(enc_depths) + list(dec_depths)),
@@ -199,6 +201,7 @@ class PointTransformerV3CA(nn.Module):
             raise NotImplementedError("all patch sizes must be equal")
         self.context_channels = int(self._context_width(ctx_channels, pdnorm_context_channels))
         self.num_stages = len(enc_depths)
+        self.qk_norm = bool(qk_norm)
         self.order = list(order)
         self.shuffle_orders = shuffle_orders
         self.proj_drop, self.attn_drop = float(proj_drop), float(attn_drop)

@@ -2,9 +2,13 @@
 
     python tools/adanorm_bench.py [--steps 20] [--windows 5] [--out path.json]
     python tools/adanorm_bench.py --rehearsal [--steps 20] [--windows 5] [--out path.json]
+    python tools/adanorm_bench.py --presets adanorm_v1,adanorm_v1_plain [--steps 20] [--windows 5] [--out path.json]
 
 The two models alternate window by window in one process (same batch, same warm-up); each reports the median of its
 windows.  The AdaNorm batch carries one instruction token per cloud (txt_reduce 'mean', instr_embed_type 'last').
+
+--presets A,B: two presets of config.preset() instead (built through policy.MODEL_FACTORY), e.g. the AdaNorm policy with and
+without q/k LayerNorm in the patch attention; reports both medians, the window rates, B over A and the library hash.
 
 --rehearsal: the one-rank RCCL rehearsal of the data-parallel AdaNorm step (LOTUS_FORCE_COLLECTIVES=1, nccl backend: every
 collective of the step goes through the real library on one device) against the plain AdaNorm step, alternating windows in one
@@ -42,13 +46,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--rehearsal", action="store_true", help="one-rank RCCL data-parallel step against the plain AdaNorm step")
+    ap.add_argument("--presets", default=None, help="A,B: two presets of config.preset() to alternate instead of AdaNorm / CA")
     a = ap.parse_args()
     if a.rehearsal:
         return rehearsal(a)
     torch.manual_seed(0)
     batch = au.last_token_batch(synth.augment_clouds(synth.synth_batch(16, 4096, seed=0), seed=1))
-    models = {"adanorm": SimplePolicyPTV3AdaNorm(lcfg.preset("adanorm_v1")).cuda().train(),
-              "ca": SimplePolicyPTV3CA(lcfg.preset("v1")).cuda().train()}
+    if a.presets:
+        from robot_3dlotus_amd.policy import MODEL_FACTORY
+
+        names = a.presets.split(",")
+        assert len(names) == 2 and names[0] != names[1], "--presets takes two different preset names: A,B"
+        models = {}
+        for n in names:
+            cfg = lcfg.preset(n)
+            models[n] = MODEL_FACTORY[cfg.model_class](cfg).cuda().train()
+    else:
+        models = {"adanorm": SimplePolicyPTV3AdaNorm(lcfg.preset("adanorm_v1")).cuda().train(),
+                  "ca": SimplePolicyPTV3CA(lcfg.preset("v1")).cuda().train()}
     b = _dev(batch)
 
     def step(m):
@@ -72,7 +87,13 @@ def main():
             rates[k].append(16 * a.steps / (time.perf_counter() - t0))
     res = {k: float(np.median(v)) for k, v in rates.items()}
     res["windows"] = rates
-    res["adanorm_over_ca"] = res["adanorm"] / res["ca"]
+    ka, kb = list(models)
+    res[f"{ka}_over_{kb}" if not a.presets else f"{kb}_over_{ka}"] = (res[ka] / res[kb]) if not a.presets else (res[kb] / res[ka])
+    if a.presets:
+        import hashlib
+
+        from robot_3dlotus_amd import _capi
+        res["library_sha256_16"] = hashlib.sha256(open(_capi.LIB_PATH, "rb").read()).hexdigest()[:16]
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
