@@ -654,6 +654,38 @@ int lotus_reg_loss_fwd(const float* ae, const float* gt, const float* xt, const 
                        void* stream);
 int lotus_reg_loss_bwd(const float* dae, const float* dpos, const float* gl, float pos_w, float rot_w, int B, int W, float* dae_out,
                        float* dpos_out, void* stream);
+/* The soft trajectory head of the motion planner, ActionHead.forward with pos_pred_type 'heatmap_mlp',
+ * genrobo3d/models/motion_planner_ptv3.py:55-62,89-109, for all T <= 8 steps in one pass over the point features.  base [n][C] = the
+ * point-feature part of heatmap_mlp.0 (shared by the steps), bias [T][C] = its step-embedding part + bias, w3 [4][C], b3 [4]
+ * (4 <= C <= 2048, C % 4 == 0).  Step t, row i: h_ti = dropout(LeakyReLU_0.02(base_i + bias_t)) -- never written to memory --,
+ * e[t][i] = h_ti w3^T + b3 ([T][n][4], kept for backward), and per cloud b:
+ *   xt[b][t] = sum_i softmax_i(e[t][i][0] / temp) (pc_i[0:3] + e[t][i][1:4]),  stats[b][t] = (max, log-sum-exp) of e[t][i][0] / temp
+ * exactly as lotus_softpos_fwd forms them (maximum subtracted, double sums, (cloud, row chunk) grid merged in fixed order: no atomics,
+ * bit-reproducible).  The dropout mask of step t is the one lotus_step_act_fwd makes from the sub-seed splitmix64(seed, t) (element
+ * index row * C + column): the pass equals lotus_step_act_fwd followed by lotus_softpos_fwd, step by step. */
+size_t lotus_mp_softpos_workspace(int B, int T);
+int lotus_mp_softpos_fwd(const float* base, const float* bias, const float* w3, const float* b3, const float* pc, long ld,
+                         const int* off, int B, int n, int C, int T, double temp, float drop_p, unsigned long long seed, float* e,
+                         float* xt, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+/* Backward of the pass above from g [B][T][3] = dL / dxt (autograd of motion_planner_ptv3.py:98-109), one pass over the rows: de_t as
+ * lotus_softpos_bwd forms it, h_t and the mask regenerated, dpre_t = (de_t w3) mask LeakyReLU'(base + bias_t);
+ *   dbase [n][C] = sum_t dpre_t (written once),  dbias [T][C] = column sums of dpre_t,  dw3 [4][C] = sum_t de_t^T h_t,  db3 [4] = sum_t
+ * colsum de_t (written, not accumulated; per-block partials reduced in fixed order).  batch [n] = cloud of row i.  A step whose g is
+ * zero contributes exact zeros. */
+size_t lotus_mp_softpos_bwd_workspace(int n, int C, int T);
+int lotus_mp_softpos_bwd(const float* g, const float* base, const float* bias, const float* w3, const float* e, const float* pc,
+                         long ld, const int* batch, const double* stats, const float* xt, int B, int n, int C, int T, double temp,
+                         float drop_p, unsigned long long seed, float* dbase, float* dbias, float* dw3, float* db3,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* compute_loss of the motion planner with the soft position, motion_planner_ptv3.py:338-397 ('heatmap_mlp' / 'euler_disc'), one
+ * launch, double arithmetic.  Rows and columns as lotus_mp_loss_fwd (ae [B*T][nrot*3 + 2], gt [B*T][ga] with the position in columns
+ * 0..2, stop, mask [B*T]); xt [B*T][3] from lotus_mp_softpos_fwd.  pos = sum mask |xt - gt[0:3]|^2 / sum mask / 3 (:340-342: one
+ * global normalisation); rot, open, stop and losses[5] = pos, rot, open, stop, total as lotus_mp_loss_fwd.  dae / dxt keep the partial
+ * derivatives for lotus_mp_reg_loss_bwd, which scales them by the upstream gradient gl[5] (device); rows with mask 0 get exact zeros. */
+int lotus_mp_reg_loss_fwd(const float* ae, const float* gt, const float* stop, const float* mask, const float* xt, int B, int T,
+                          int nrot, int ga, float pos_w, float rot_w, float* losses, float* dae, float* dxt, void* stream);
+int lotus_mp_reg_loss_bwd(const float* dae, const float* dxt, const float* gl, float pos_w, float rot_w, int B, int T, int nrot,
+                          float* dae_out, float* dxt_out, void* stream);
 
 #ifdef __cplusplus
 }

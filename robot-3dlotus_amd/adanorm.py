@@ -321,6 +321,32 @@ class AdaStemFn(torch.autograd.Function):
         return dx, dmod, dcw, dg, db, None, None, None, None, None, None
 
 
+class AdaStemGroupsFn(torch.autograd.Function):
+    """AdaStemFn for an input given as two column groups with a weight each: SubMConv3d_5 is linear in its input columns, so
+    conv(W, [xa | xb]) = conv(Wa, xa) + conv(Wb, xb) — two thin convolutions, the second adding onto the first, and one weight
+    gradient per group.  The groups are never concatenated (the motion planner: point features | one-hot label, <= 8 columns each,
+    where the concatenation would be wider than the thin-input kernels take)."""
+
+    @_fwd
+    def forward(ctx, xa, xb, mod, wa, wb, g, b, rmean, rvar, lvl, training, bank, j):
+        ca = ops.conv_fwd(xa, wa, None, lvl.nbr125, lvl.order[0])
+        c = ops.conv_fwd(xb, wb, None, lvl.nbr125, lvl.order[0], add=ca)
+        y, mean, invstd = adabn_fwd(c, g, b, rmean, rvar, mod, lvl, training)
+        ctx.meta = (lvl, training, bank, j, wa.shape, wb.shape)
+        ctx.save_for_backward(xa, xb, mod, g, b, c, mean, invstd)
+        return y
+
+    @_joined
+    def backward(ctx, dy):
+        xa, xb, mod, g, b, c, mean, invstd = ctx.saved_tensors
+        lvl, training, bank, j, wa_shape, wb_shape = ctx.meta
+        dmod = bank.grad_slice(j)
+        dc, dg, db = adabn_bwd(dy.contiguous(), c, mean, invstd, g, b, mod, dmod, lvl, training)
+        dwa, _ = ops.conv_wgrad(dc, xa, wa_shape, lvl.nbr125, need_bias=False)
+        dwb, _ = ops.conv_wgrad(dc, xb, wb_shape, lvl.nbr125, need_bias=False)
+        return None, None, dmod, dwa, dwb, dg, db, None, None, None, None, None, None
+
+
 class AdaPoolFn(torch.autograd.Function):
     """SerializedPooling: GELU(PDNorm_BN(segment_max(Linear(x))))   (model.py:760-790); the norm sees the pooled level's clouds."""
 
@@ -541,8 +567,19 @@ class PointTransformerV3AdaNorm(PointTransformerV3CA):
         fw.mods = ModAllFn.apply(fw.context, fw.bank, *self._mod_params())
         st = self.embedding.stem
         nb, j = st.norm.norm, self._pd_index[id(st.norm)]
-        x = AdaStemFn.apply(feat, fw.mods[j], st.conv.weight, nb.weight, nb.bias, nb.running_mean, nb.running_var,
-                            fw.levels[0], fw.training, fw.bank, j)
+        groups = data_dict.get("stem_groups")
+        if groups is not None:
+            # (xa, xb, wa, wb): the input as two column groups, each with its weight [cout, 5, 5, 5, columns of the group] — a
+            # differentiable function of st.conv.weight (the motion planner: point features | one-hot point label)
+            xa, xb, wa, wb = groups
+            if xa.shape[1] > 8 or xb.shape[1] > 8:
+                raise NotImplementedError(f"stem_groups of {xa.shape[1]} and {xb.shape[1]} columns: the thin-input stem "
+                                          "convolution takes at most 8 columns per group")
+            x = AdaStemGroupsFn.apply(xa, xb, fw.mods[j], wa, wb, nb.weight, nb.bias, nb.running_mean, nb.running_var,
+                                      fw.levels[0], fw.training, fw.bank, j)
+        else:
+            x = AdaStemFn.apply(feat, fw.mods[j], st.conv.weight, nb.weight, nb.bias, nb.running_mean, nb.running_var,
+                                fw.levels[0], fw.training, fw.bank, j)
         ops.sync_side_stream()  # the packed convolution weights
         return x
 

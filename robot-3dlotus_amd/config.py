@@ -178,18 +178,36 @@ REG_OVERRIDES = {"tiny_reg": TINY_OVERRIDES + REG_SWITCHES, "v1_reg": V1_OVERRID
                  "adanorm_tiny_reg": ADANORM_OVERRIDES["adanorm_tiny"] + REG_SWITCHES}
 
 
+# MotionPlannerPTV3AdaNorm (motion_planner_ptv3.py:151-397).  'mp_yaml' is the MODEL section of motion_planner_ptv3.yaml as
+# shipped: _YAML_MODEL + _YAML_MP_DELTA without the keys that YAML does not have (use_step_id is commented out there, :152).
+# 'mp_ada_tiny': the tiny widths of BASELINE configs[0] under the YAML's own switches (adaptive PDNorm, qk_norm False, heatmap_mlp
+# positions, pose context); the job-script overrides it keeps are the ones about the networks' size and the 4-column input.
+_YAML_MP_ABSENT = ("use_step_id",)
+MP_ADA_OVERRIDES = {"mp_yaml": [], "mp_ada_tiny": [
+    "ptv3_config.in_channels", "4", "ptv3_config.drop_path", "0.0", "action_config.dropout", "0.2", "action_config.dim_actions", "7",
+    "action_config.pos_bins", "15"] + TINY_OVERRIDES[len(V1_OVERRIDES):]}
+
+
 def preset(name="v1"):
     """'v1' / 'tiny': 3D-LOTUS policy; 'peract': the RLBench-18task (PerAct) variant of BASELINE configs[4] (same network;
     its bf16 compute mode is ops.set_gemm_precision("bf16")); 'mp' / 'mp_tiny': 3D-LOTUS++ motion planner (configs[3]);
     'adanorm_v1' / 'adanorm_tiny' / 'adanorm_tinyctx': the policy networks as SimplePolicyPTV3AdaNorm (adaptive PDNorm);
     'adanorm_yaml': simple_policy_ptv3.yaml as shipped (= load_model_config(None)); 'adanorm_tiny_plain' / 'adanorm_v1_plain':
     adanorm_tiny / adanorm_v1 with qk_norm False;
-    'tiny_reg' / 'v1_reg' / 'adanorm_tiny_reg': their base preset with the regression head (heatmap_mlp positions, euler)."""
+    'tiny_reg' / 'v1_reg' / 'adanorm_tiny_reg': their base preset with the regression head (heatmap_mlp positions, euler);
+    'mp_yaml': motion_planner_ptv3.yaml as shipped (MotionPlannerPTV3AdaNorm, soft trajectory head); 'mp_ada_tiny': its tiny width."""
     if name in ("mp", "mp_tiny", "mp_tinyctx"):
         model = copy.deepcopy(_YAML_MODEL)
         model["model_class"] = _YAML_MP_DELTA["model_class"]
         model["action_config"].update(_YAML_MP_DELTA["action_config"])
         return to_cfg(merge_overrides(model, {"mp": MP_OVERRIDES, "mp_tiny": MP_TINY_OVERRIDES, "mp_tinyctx": MP_TINYCTX_OVERRIDES}[name]))
+    if name in MP_ADA_OVERRIDES:
+        model = copy.deepcopy(_YAML_MODEL)
+        model["model_class"] = _YAML_MP_DELTA["model_class"]
+        model["action_config"].update(_YAML_MP_DELTA["action_config"])
+        for k in _YAML_MP_ABSENT:
+            del model["action_config"][k]
+        return to_cfg(merge_overrides(model, MP_ADA_OVERRIDES[name]))
     if name in ADANORM_OVERRIDES:
         return load_model_config(None, ADANORM_OVERRIDES[name])
     if name in REG_OVERRIDES:

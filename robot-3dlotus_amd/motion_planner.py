@@ -11,6 +11,9 @@ What runs where: every matrix product over points, the sparse convolutions, atte
 heatmap cross entropy are lotus-hip kernels (ops.*Fn); the [B, T]-sized rotation / openness / stop losses, the
 trajectory-embedding bias (5 x 64 floats) and the effective stem weight (see prepare_ptv3_batch) are a few ATen
 launches on small tensors.
+
+MotionPlannerPTV3AdaNorm (:151-397, the class motion_planner_ptv3.yaml names) is the same planner on the adaptive-PDNorm
+backbone with the soft trajectory head (pos_pred_type 'heatmap_mlp'): see the class.
 """
 import torch
 import torch.nn as nn
@@ -23,20 +26,32 @@ from .ptv3 import PointTransformerV3CA
 
 
 class TrajectoryActionHead(nn.Module):
-    """Parameter layout of motion_planner_ptv3.py:20-75 for (max, heatmap_disc, euler_disc)."""
+    """Parameter layout of motion_planner_ptv3.py:20-75 for (max, heatmap_disc, euler_disc) and, with `soft_pos` (set by
+    MotionPlannerPTV3AdaNorm only), for (max, heatmap_mlp, euler_disc): heatmap_mlp.3 then has 1 + 3 outputs (:55-62)."""
 
     def __init__(self, reduce, pos_pred_type, rot_pred_type, hidden_size, dim_actions, max_traj_len, dropout=0,
-                 voxel_size=0.01, euler_resolution=5, ptv3_config=None, pos_bins=50, traj_embed_size=64):
+                 voxel_size=0.01, euler_resolution=5, ptv3_config=None, pos_bins=50, traj_embed_size=64, soft_pos=False):
         super().__init__()
-        if (reduce, pos_pred_type, rot_pred_type) != ("max", "heatmap_disc", "euler_disc"):
-            raise NotImplementedError("lotus-hip builds the published head: reduce=max, heatmap_disc, euler_disc")
+        if not soft_pos:
+            if (reduce, pos_pred_type, rot_pred_type) != ("max", "heatmap_disc", "euler_disc"):
+                raise NotImplementedError("lotus-hip builds the published head: reduce=max, heatmap_disc, euler_disc")
+        else:
+            if reduce != "max":
+                raise NotImplementedError(f"reduce={reduce!r}: lotus-hip builds the trajectory head with reduce='max' only")
+            if pos_pred_type not in ("heatmap_disc", "heatmap_mlp"):
+                raise NotImplementedError(f"pos_pred_type={pos_pred_type!r}: lotus-hip builds the trajectory head with "
+                                          "'heatmap_mlp' (MotionPlannerPTV3AdaNorm) and 'heatmap_disc'")
+            if rot_pred_type != "euler_disc":
+                raise NotImplementedError(f"rot_pred_type={rot_pred_type!r}: lotus-hip builds the trajectory head with 'euler_disc' only")
         if traj_embed_size <= 0:
             raise NotImplementedError("traj_embed_size == 0 (single-step head) is the SimplePolicy head; use that")
+        self.pos_pred_type = pos_pred_type
         self.euler_resolution, self.euler_bins, self.pos_bins = euler_resolution, 360 // euler_resolution, pos_bins
         self.max_traj_len, self.hidden_size, self.dropout = max_traj_len, hidden_size, float(dropout)
         self.traj_embedding = nn.Embedding(max_traj_len, traj_embed_size)
         self.heatmap_mlp = nn.Sequential(nn.Linear(hidden_size + traj_embed_size, hidden_size), nn.LeakyReLU(0.02),
-                                         nn.Dropout(dropout), nn.Linear(hidden_size, 3 * pos_bins * 2))
+                                         nn.Dropout(dropout),
+                                         nn.Linear(hidden_size, 3 * pos_bins * 2 if pos_pred_type == "heatmap_disc" else 4))
         self.action_mlp = nn.Sequential(nn.Linear(hidden_size + traj_embed_size, hidden_size), nn.LeakyReLU(0.02),
                                         nn.Dropout(dropout), nn.Linear(hidden_size, self.euler_bins * 3 + 1 + 1))
 
@@ -51,7 +66,7 @@ class MotionPlannerPTV3CA(BaseModel):
         # the reference adds pc_label_channels into config.ptv3_config.in_channels in place
         # (motion_planner_ptv3.py:405-408); the caller's config is left untouched here
         p3["in_channels"] = config.ptv3_config.in_channels + act.pc_label_channels
-        self.ptv3_model = PointTransformerV3CA(**p3)
+        self.ptv3_model = self._make_backbone(p3, act)
         self.pc_label_embedding = nn.Embedding(4, act.pc_label_channels)   # 0 obstacle, 1 robot, 2 object, 3 target
         self.txt_fc = nn.Linear(act.txt_ft_size, act.context_channels)
         if act.txt_reduce == "attn":
@@ -61,8 +76,13 @@ class MotionPlannerPTV3CA(BaseModel):
         self.act_proj_head = TrajectoryActionHead(
             act.reduce, act.pos_pred_type, act.rot_pred_type, config.ptv3_config.dec_channels[0], act.dim_actions,
             act.max_traj_len, dropout=act.dropout, voxel_size=act.voxel_size, pos_bins=act.pos_bins,
-            traj_embed_size=act.traj_embed_size)
+            traj_embed_size=act.traj_embed_size, soft_pos=self.soft_pos)
         self.apply(self._init_weights)
+
+    soft_pos = False  # the trajectory head's 'heatmap_mlp' option: MotionPlannerPTV3AdaNorm only
+
+    def _make_backbone(self, p3, act):
+        return PointTransformerV3CA(**p3)
 
     def prepare_ptv3_batch(self, batch):
         """motion_planner_ptv3.py:433-463: feat = [pc_fts | label embedding], context = txt_fc(txt_embeds)."""
@@ -196,3 +216,137 @@ class MotionPlannerPTV3CA(BaseModel):
                                  batch["gt_trajs_stop"].float().reshape(-1).contiguous(), m.reshape(B, T).contiguous(),
                                  (ae.shape[-1] - 2) // 3, lc.pos_weight, lc.rot_weight)
         return {"pos": L[0], "rot": L[1], "open": L[2], "stop": L[3], "total": L[4]}
+
+
+class MotionPlannerPTV3AdaNorm(MotionPlannerPTV3CA):
+    """motion_planner_ptv3.py:151-397, the model class of genrobo3d/configs/rlbench/motion_planner_ptv3.yaml: the instruction
+    (+ pose) enters the point backbone through adaptive PDNorm (adanorm.PointTransformerV3AdaNorm), one context vector per
+    cloud, and the trajectory head predicts soft positions (pos_pred_type 'heatmap_mlp': ops.TrajSoftPosFn, ops.TrajRegLossFn)
+    or the published heat maps ('heatmap_disc').  Forward contract, kwargs and `last_pred` are MotionPlannerPTV3CA's; with
+    'heatmap_mlp' last_pred[0] is xt [B, T, 3] and the final position is xt whatever compute_final_action says (:243).
+    fp32 activation storage; data parallel through parallel.GradReducer + SyncBatchNorm statistics like the AdaNorm policy."""
+    soft_pos = True
+
+    def _make_backbone(self, p3, act):
+        from .adanorm import PointTransformerV3AdaNorm
+
+        p3.setdefault("pdnorm_only_decoder", False)  # (motion_planner_ptv3.py:157-160)
+        p3["pdnorm_context_channels"] = act.context_channels
+        if act.txt_reduce not in ("mean", "attn"):
+            raise NotImplementedError(f"txt_reduce={act.txt_reduce!r}: MotionPlannerPTV3AdaNorm builds 'mean' and 'attn'")
+        return PointTransformerV3AdaNorm(**p3)
+
+    def _point_input(self, batch):
+        """-> (pc [N, c_pc] fp32 contiguous, one-hot label [N, 4]); prefetch() may have built them already."""
+        pres = getattr(self, "_pre", None) or []
+        pre = next((q for q in pres if q[0] is batch["pc_fts"] and q[1] is batch["pc_labels"]), None)
+        self._pre = [q for q in pres if q is not pre][-1:]  # (at most one more: the batch after this one)
+        if pre is not None:
+            return pre[2], pre[3]
+        return batch["pc_fts"].float().contiguous(), F.one_hot(batch["pc_labels"].long(), 4).float()
+
+    def prepare_ptv3_batch(self, batch):
+        """motion_planner_ptv3.py:190-222: feat = [pc_fts | label embedding], context = one vector per cloud (txt_fc reduced by
+        'mean' — one token per cloud — or 'attn', plus the pose embedding).  The stem convolution is linear in its input
+        columns, so its two column groups are convolved separately (adanorm.AdaStemGroupsFn): the point features with
+        W[..., :c_pc], the one-hot label with W[..., c_pc:] E^T (the embedding folded into the weight as MotionPlannerPTV3CA
+        does); autograd carries both weight gradients back into stem.conv.weight and the embedding table."""
+        from .adanorm import cloud_context
+
+        act = self.config.action_config
+        pc, onehot = self._point_input(batch)
+        c_pc = pc.shape[1]
+        if c_pc > 8:
+            raise NotImplementedError(f"MotionPlannerPTV3AdaNorm: pc_fts with {c_pc} > 8 columns (the thin-input stem convolution "
+                                      "takes at most 8 per column group)")
+        W, E = self.ptv3_model.embedding.stem.conv.weight, self.pc_label_embedding.weight
+        if W.shape[-1] != c_pc + E.shape[1]:
+            raise ValueError(f"pc_fts has {c_pc} columns, ptv3_config.in_channels is {W.shape[-1] - E.shape[1]}")
+        w_pc, w_lab = W[..., :c_pc].contiguous(), torch.matmul(W[..., c_pc:], E.t()).contiguous()
+        txt = batch["txt_embeds"].contiguous()
+        lens = [int(v) for v in batch["txt_lens"]]
+        if act.txt_reduce == "mean" and any(n != 1 for n in lens):
+            raise ValueError(f"txt_reduce='mean' takes one instruction token per cloud (instr_embed_type='last'); txt_lens={lens}")
+        ctx = ops.LinearFn.apply(txt, self.txt_fc.weight, self.txt_fc.bias)
+        if act.txt_reduce == "attn":
+            ctx = cloud_context(ctx, ops.LinearFn.apply(txt, self.txt_attn_fc.weight, self.txt_attn_fc.bias), lens)
+        if act.use_ee_pose:
+            ctx = ctx + self.pose_embedding(batch["ee_poses"].float())
+        B = len(batch["npoints_in_batch"])
+        return {"coord": pc[:, :3], "grid_size": act.voxel_size, "offset": batch["offset"], "feat": pc,
+                "stem_groups": (pc, onehot, w_pc, w_lab), "context": ctx.contiguous(),
+                "counts": list(batch["npoints_in_batch"]), "context_counts": [1] * B}
+
+    @torch.no_grad()
+    def prefetch(self, batch):
+        """Input-pipeline hook, as MotionPlannerPTV3CA.prefetch: build the network input of `batch` and start its integer
+        front-end on the side stream; the following forward(batch) must get the same (device) batch."""
+        batch = self.prepare_batch(batch)
+        pc, onehot = batch["pc_fts"].float().contiguous(), F.one_hot(batch["pc_labels"].long(), 4).float()
+        self._pre = ((getattr(self, "_pre", None) or []) + [(batch["pc_fts"], batch["pc_labels"], pc, onehot)])[-2:]
+        self.ptv3_model.prefetch({"coord": pc[:, :3], "grid_size": self.config.action_config.voxel_size, "offset": batch["offset"],
+                                  "feat": pc, "counts": list(batch["npoints_in_batch"]),
+                                  "context_counts": [1] * len(batch["npoints_in_batch"])})
+
+    def forward(self, batch, compute_loss=False, **kwargs):
+        if self.act_storage == "bf16":
+            raise NotImplementedError("MotionPlannerPTV3AdaNorm: act_storage='bf16' is not built (fp32 activations only)")
+        if not self.ptv3_model.qk_norm:
+            mode = self.gemm_precision or ops.get_gemm_precision()
+            if mode != "fp32":  # the patch attention without q/k LayerNorm exists as exact-fp32 kernels only
+                raise NotImplementedError(f"MotionPlannerPTV3AdaNorm with qk_norm=False is built for gemm_precision None / 'fp32' "
+                                          f"only, got {mode!r}")
+        return super().forward(batch, compute_loss, **kwargs)
+
+    def _forward(self, batch, compute_loss=False, **kwargs):
+        if self.act_proj_head.pos_pred_type != "heatmap_mlp":
+            return super()._forward(batch, compute_loss, **kwargs)
+        batch = self.prepare_batch(batch)
+        dev = self.hip_device(batch)
+        act, head = self.config.action_config, self.act_proj_head
+        d = self.prepare_ptv3_batch(batch)
+        last = self.ptv3_model(d, return_dec_layers=True)[-1]
+        x, lvl = last.feat, last.level
+        B, T, C = len(lvl.counts), head.max_traj_len, head.hidden_size
+        eb = head.euler_bins
+        p = head.dropout if self.training else 0.0
+        hm, am = head.heatmap_mlp, head.action_mlp
+        te = head.traj_embedding.weight                                         # [T, E]
+
+        # heatmap branch, motion_planner_ptv3.py:89-109: Linear([x | te_t]) = x Wx^T + (te_t Wt^T + b); the T hidden layers,
+        # the 4-column product, the per-cloud softmax and the weighted coordinates are one pass over `base`
+        base = ops.LinearFn.apply(x, hm[0].weight[:, :C].contiguous(), None)                       # [N, C]
+        step_bias = F.linear(te, hm[0].weight[:, C:], hm[0].bias)                                  # [T, C]
+        xt = ops.TrajSoftPosFn.apply(base, step_bias.contiguous(), hm[3].weight, hm[3].bias, d["feat"], lvl,
+                                     float(act.get("pos_heatmap_temp", 1)), p,
+                                     ops.mix_seed(self.ptv3_model.last_seed, 2000))                # [B, T, 3]
+        # action branch, :116-120,139-146, as MotionPlannerPTV3CA
+        pc = ops.CloudMaxFn.apply(x, lvl)                                                         # [B, C]
+        pcs = torch.cat([pc.unsqueeze(1).expand(-1, T, -1), te.to(pc.dtype).unsqueeze(0).expand(B, -1, -1)], -1).reshape(B * T, -1)
+        a = F.dropout(F.leaky_relu(ops.LinearFn.apply(pcs, am[0].weight, am[0].bias), 0.02), p, self.training)
+        ae = ops.LinearFn.apply(a, am[3].weight, am[3].bias).view(B, T, -1)
+        pred_rot = ae[..., :eb * 3].reshape(B, T, eb, 3)
+        pred_open, pred_stop = ae[..., -2], ae[..., -1]
+        self.last_pred = (xt, pred_rot, pred_open, pred_stop)
+
+        losses = None
+        if compute_loss:
+            lc = self.config.loss_config
+            L = ops.TrajRegLossFn.apply(ae.reshape(B * T, -1), xt.reshape(B * T, 3),
+                                        batch["gt_trajs"].float().reshape(B * T, -1).contiguous(),
+                                        batch["gt_trajs_stop"].float().reshape(-1).contiguous(),
+                                        batch["traj_masks"].float().reshape(B, T).contiguous(), eb, lc.pos_weight, lc.rot_weight)
+            losses = {"pos": L[0], "rot": L[1], "open": L[2], "stop": L[3], "total": L[4]}
+        decode = kwargs.get("compute_final_action", True)
+        if compute_loss and self.training and not decode and not kwargs.get("decode_actions", False):
+            return None, losses                                  # trainer discards the actions (see policy.py)
+        # :243,276-294: the continuous position is final as it is; float64 quaternions promote the whole action
+        quat = self.decode_euler_disc(pred_rot.reshape(B * T, eb, 3), head.euler_resolution, dev).reshape(B, T, 4)
+        final = torch.cat([xt.detach(), quat, pred_open.detach().unsqueeze(-1), pred_stop.detach().unsqueeze(-1)], -1)
+        return (final, losses) if compute_loss else final
+
+    def pred_pos(self):
+        """Last forward's position: xt [B, T, 3] ('heatmap_mlp'), or the logits in the reference layout ('heatmap_disc')."""
+        if self.act_proj_head.pos_pred_type == "heatmap_mlp":
+            return self.last_pred[0]
+        return super().pred_pos()

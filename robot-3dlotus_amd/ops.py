@@ -2100,6 +2100,70 @@ class TrajLossFn(torch.autograd.Function):
         return dae_o, dce_o, None, None, None, None, None, None
 
 
+class TrajSoftPosFn(torch.autograd.Function):
+    """Heat-map branch of the soft trajectory head for ALL steps in one pass (motion_planner_ptv3.py:89-109, pos_pred_type
+    'heatmap_mlp'): xt[b, t] = sum_i softmax_i(e_ti0 / temp) (coord_i + e_ti[1:4]) with e_t = dropout(LeakyReLU(base +
+    step_bias[t])) W3^T + b3.  The hidden layers never reach memory, forward or backward (lotus_mp_softpos_fwd / _bwd); the
+    mask of step t is StepHeadFn's (mix_seed(seed, t)).  pc_fts [N, >= 3] holds the coordinates.  Returns xt [B, T, 3]."""
+
+    @_fwd
+    def forward(ctx, base, step_bias, w3, b3, pc_fts, lvl, temp, drop_p, seed):
+        assert not _capi.BF16, "the soft trajectory head runs with fp32 activation storage"
+        T = step_bias.shape[0]
+        N, C = base.shape
+        B = len(lvl.counts)
+        dev = base.device
+        e = torch.empty(T, N, 4, dtype=torch.float32, device=dev)
+        xt = torch.empty(B, T, 3, dtype=torch.float32, device=dev)
+        stats = torch.empty(B, T, 2, dtype=torch.float64, device=dev)
+        ws = _ws(query("lotus_mp_softpos_workspace", B, T), dev)
+        call("lotus_mp_softpos_fwd", base, step_bias, w3, b3, pc_fts, pc_fts.stride(0), lvl.off, B, N, C, T, float(temp),
+             float(drop_p), int(seed), e, xt, stats, ws, ws.numel())
+        ctx.save_for_backward(base, step_bias, w3, e, pc_fts, stats, xt)
+        ctx.meta = (lvl, float(temp), float(drop_p), int(seed))
+        return xt
+
+    @_joined
+    def backward(ctx, g):
+        base, step_bias, w3, e, pc_fts, stats, xt = ctx.saved_tensors
+        lvl, temp, p, seed = ctx.meta
+        T = step_bias.shape[0]
+        N, C = base.shape
+        dbase, dsb, dw3 = torch.empty_like(base), torch.empty_like(step_bias), torch.empty_like(w3)
+        db3 = torch.empty(4, dtype=torch.float32, device=base.device)
+        ws = _ws(query("lotus_mp_softpos_bwd_workspace", N, C, T), base.device)
+        call("lotus_mp_softpos_bwd", g.contiguous().float(), base, step_bias, w3, e, pc_fts, pc_fts.stride(0), lvl.batch, stats, xt,
+             len(lvl.counts), N, C, T, temp, p, seed, dbase, dsb, dw3, db3, ws, ws.numel())
+        return dbase, dsb, dw3, db3, None, None, None, None, None
+
+
+class TrajRegLossFn(torch.autograd.Function):
+    """The [B, T]-sized losses of the motion planner with the soft position in one launch (motion_planner_ptv3.py:338-397):
+    masked MSE of xt [B*T, 3] with ONE global normalisation, masked rotation cross entropy, openness / stop BCE.  Returns the
+    vector (pos, rot, open, stop, total)."""
+
+    @_fwd
+    def forward(ctx, ae, xt, gt, stop, mask, nrot, pos_w, rot_w):
+        assert not _capi.BF16, "the soft trajectory head runs with fp32 activation storage"
+        B, T = mask.shape
+        ae, xt = ae.contiguous(), xt.contiguous()
+        losses = torch.empty(5, dtype=torch.float32, device=ae.device)
+        dae = torch.empty(ae.shape, dtype=torch.float32, device=ae.device)
+        dxt = torch.empty_like(xt)
+        call("lotus_mp_reg_loss_fwd", ae, gt, stop, mask, xt, B, T, nrot, gt.shape[-1], float(pos_w), float(rot_w), losses, dae, dxt)
+        ctx.save_for_backward(dae, dxt)
+        ctx.dims = (B, T, nrot, float(pos_w), float(rot_w))
+        return losses
+
+    @_joined
+    def backward(ctx, g):
+        dae, dxt = ctx.saved_tensors
+        B, T, nrot, pos_w, rot_w = ctx.dims
+        dae_o, dxt_o = torch.empty_like(dae), torch.empty_like(dxt)
+        call("lotus_mp_reg_loss_bwd", dae, dxt, g.contiguous().float(), pos_w, rot_w, B, T, nrot, dae_o, dxt_o)
+        return dae_o, dxt_o, None, None, None, None, None, None
+
+
 class CloudMaxFn(torch.autograd.Function):
     """torch.stack([torch.max(x, 0)[0] for x in torch.split(feat, npoints_in_batch)]),
     motion_planner_ptv3.py:117-119 / simple_policy_ptv3.py:117-119."""

@@ -420,9 +420,9 @@ class SimplePolicyPTV3AdaNorm(SimplePolicyPTV3CA):
 
 
 def _factory():
-    from .motion_planner import MotionPlannerPTV3CA
+    from .motion_planner import MotionPlannerPTV3AdaNorm, MotionPlannerPTV3CA
     return {"SimplePolicyPTV3CA": SimplePolicyPTV3CA, "MotionPlannerPTV3CA": MotionPlannerPTV3CA,
-            "SimplePolicyPTV3AdaNorm": SimplePolicyPTV3AdaNorm}
+            "SimplePolicyPTV3AdaNorm": SimplePolicyPTV3AdaNorm, "MotionPlannerPTV3AdaNorm": MotionPlannerPTV3AdaNorm}
 
 
 class _Factory(dict):
