@@ -687,6 +687,27 @@ int lotus_mp_reg_loss_fwd(const float* ae, const float* gt, const float* stop, c
 int lotus_mp_reg_loss_bwd(const float* dae, const float* dxt, const float* gl, float pos_w, float rot_w, int B, int T, int nrot,
                           float* dae_out, float* dxt_out, void* stream);
 
+/* ---- context stem of SimplePolicyPTV3Concat (fp32 only, no bf16 twin) --------------------------------------------------------
+ * genrobo3d/models/simple_policy_ptv3.py:457-461 repeats one context vector per cloud over the cloud's points and concatenates it to
+ * pc_fts; the 5^3 SubMConv3d of PointTransformerV3/model.py:844-853 reads the result.  The convolution is linear in its input
+ * columns and the context columns are constant over a cloud, so their share of the output is a sum over the PRESENT taps of rows of
+ * P [B][T][C], P[b][t] = W_ctx[:, t, :] ctx_b (one small dense product).  nbr [T][n] is the neighbour table of the convolution; only
+ * the sign of an entry is read (>= 0: present).  off [B + 1] = first row of every cloud (device).
+ *   lotus_ctx_taps_fwd:  y_i = add_i + sum_{t ascending, nbr[t][i] >= 0} P[b(i)][t]          (add [n][C] or null; y may not alias P)
+ *   lotus_ctx_taps_bwd:  dP[b][t] = sum_{i in cloud b, nbr[t][i] >= 0} dy_i                  (written; a tap absent from a cloud: exact 0)
+ * The cloud's [T][C] slice sits in LDS: T <= 128 (two 64-bit presence words per row), C % 4 == 0 and T x C <= 32768 floats (128 KB;
+ * C <= 260 at T = 125, C <= 256 at T = 128), B <= 65535.  Grids over (cloud, row chunk), no atomics, fixed summation order: reruns are
+ * bit-identical.  LOTUS_E_ARG before any launch on C <= 0, C % 4 != 0, T x C over the limit, T <= 0, T > 128, B <= 0, n < 0, a null or
+ * misaligned (16 bytes) pointer or a short workspace; n == 0 returns 0 without a launch. */
+size_t lotus_ctx_taps_workspace(int B, int T, int C);
+int lotus_ctx_taps_fwd(const float* P, const int* nbr, const int* off, const float* add, float* y, int B, int n, int T, int C,
+                       void* stream);
+int lotus_ctx_taps_bwd(const float* dy, const int* nbr, const int* off, float* dP, int B, int n, int T, int C, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* Diagnostic, host only: out[6] = {rows per chunk of the forward grid, its chunks (grid x) for n rows, chunks per cloud of the
+ * backward grid, rows per presence tile forward, backward, the widest C the entry points take at this T}.  Refuses what they refuse. */
+int lotus_ctx_taps_plan(int n, int B, int T, int C, int* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,16 @@ MP_ADA_OVERRIDES = {"mp_yaml": [], "mp_ada_tiny": [
     "action_config.pos_bins", "15"] + TINY_OVERRIDES[len(V1_OVERRIDES):]}
 
 
+# SimplePolicyPTV3Concat (simple_policy_ptv3.py:434-463): the context vector of a cloud is concatenated to every point's features, so
+# in_channels = columns of pc_fts + context_channels and the backbone is a plain PointTransformerV3 (no PDNorm).  'concat_yaml' is
+# the YAML's MODEL section with the class, the input width and the three PDNorm flags changed; 'concat_tiny' the tiny family
+# (7 point columns + 256) with the two optional context terms on.
+CONCAT_SWITCHES = ["model_class", "SimplePolicyPTV3Concat", "ptv3_config.pdnorm_bn", "False", "ptv3_config.pdnorm_ln", "False",
+                   "ptv3_config.pdnorm_adaptive", "False"]
+CONCAT_OVERRIDES = {"concat_yaml": CONCAT_SWITCHES + ["ptv3_config.in_channels", "262"],
+                    "concat_tiny": TINYCTX_OVERRIDES + CONCAT_SWITCHES + ["ptv3_config.in_channels", "263"]}
+
+
 def preset(name="v1"):
     """'v1' / 'tiny': 3D-LOTUS policy; 'peract': the RLBench-18task (PerAct) variant of BASELINE configs[4] (same network;
     its bf16 compute mode is ops.set_gemm_precision("bf16")); 'mp' / 'mp_tiny': 3D-LOTUS++ motion planner (configs[3]);
@@ -195,7 +205,8 @@ def preset(name="v1"):
     'adanorm_yaml': simple_policy_ptv3.yaml as shipped (= load_model_config(None)); 'adanorm_tiny_plain' / 'adanorm_v1_plain':
     adanorm_tiny / adanorm_v1 with qk_norm False;
     'tiny_reg' / 'v1_reg' / 'adanorm_tiny_reg': their base preset with the regression head (heatmap_mlp positions, euler);
-    'mp_yaml': motion_planner_ptv3.yaml as shipped (MotionPlannerPTV3AdaNorm, soft trajectory head); 'mp_ada_tiny': its tiny width."""
+    'mp_yaml': motion_planner_ptv3.yaml as shipped (MotionPlannerPTV3AdaNorm, soft trajectory head); 'mp_ada_tiny': its tiny width;
+    'concat_yaml' / 'concat_tiny': SimplePolicyPTV3Concat on the YAML's networks (in_channels 262) / the tiny ones (263)."""
     if name in ("mp", "mp_tiny", "mp_tinyctx"):
         model = copy.deepcopy(_YAML_MODEL)
         model["model_class"] = _YAML_MP_DELTA["model_class"]
@@ -212,6 +223,8 @@ def preset(name="v1"):
         return load_model_config(None, ADANORM_OVERRIDES[name])
     if name in REG_OVERRIDES:
         return load_model_config(None, REG_OVERRIDES[name])
+    if name in CONCAT_OVERRIDES:  # 'concat_yaml' / 'concat_tiny': SimplePolicyPTV3Concat
+        return load_model_config(None, CONCAT_OVERRIDES[name])
     return load_model_config(None, {"v1": V1_OVERRIDES, "tiny": TINY_OVERRIDES, "peract": PERACT_OVERRIDES,
                                     "tinydeep": TINYDEEP_OVERRIDES, "tinyctx": TINYCTX_OVERRIDES}[name])
 

@@ -419,10 +419,62 @@ class SimplePolicyPTV3AdaNorm(SimplePolicyPTV3CA):
         return super().forward(batch, compute_loss, **kwargs)
 
 
+class SimplePolicyPTV3Concat(SimplePolicyPTV3AdaNorm):
+    """simple_policy_ptv3.py:434-463: the AdaNorm policy's constructor, but the context vector of a cloud — txt_fc(txt) (+ pose)
+    (+ step) — is repeated over the cloud's points and concatenated to pc_fts, and the backbone is a plain PointTransformerV3 with
+    in_channels = columns of pc_fts + context_channels (concat.PointTransformerV3Plain: the concatenation is never formed, the
+    context columns enter the stem as per-cloud tap sums).  Head, losses, decode, forward contract and `last_pred` are
+    SimplePolicyPTV3CA's; the state_dict has the reference's layout (stem weight [cout, 5, 5, 5, c_pc + 256]; `txt_attn_fc` for
+    txt_reduce == 'attn', which the reference builds and never uses).  fp32 activations, gemm_precision None / 'fp32'."""
+
+    def _make_backbone(self, p3, act):
+        from .concat import PointTransformerV3Plain
+
+        p3["pdnorm_context_channels"] = act.context_channels
+        return PointTransformerV3Plain(**p3)
+
+    def _check_pc(self, pc_fts):
+        from .concat import MAX_PC_COLUMNS
+
+        c_pc, cc, cin = pc_fts.shape[1], self.config.action_config.context_channels, self.ptv3_model.in_channels
+        if c_pc > MAX_PC_COLUMNS:
+            raise NotImplementedError(f"pc_fts of {c_pc} columns: the thin-input stem convolution of SimplePolicyPTV3Concat takes at "
+                                      f"most {MAX_PC_COLUMNS}")
+        if cin != c_pc + cc:
+            raise ValueError(f"SimplePolicyPTV3Concat: in_channels={cin} != {c_pc} columns of pc_fts + {cc} context_channels")
+
+    def prepare_ptv3_batch(self, batch):
+        """simple_policy_ptv3.py:438-463: ctx = txt_fc(txt_embeds) (+ pose_embedding) (+ stepid_embedding), one row per cloud — the
+        reference repeats row b over the points of cloud b, so the instruction must be ONE token per cloud."""
+        lens = [int(v) for v in batch["txt_lens"]]
+        if any(n != 1 for n in lens):
+            raise ValueError(f"SimplePolicyPTV3Concat takes one instruction token per cloud (instr_embed_type='last'); txt_lens={lens}")
+        self._check_pc(batch["pc_fts"])
+        act = self.config.action_config
+        ctx = ops.LinearFn.apply(batch["txt_embeds"].contiguous(), self.txt_fc.weight, self.txt_fc.bias)
+        if act.use_ee_pose:
+            ctx = ctx + self.pose_embedding(batch["ee_poses"].float())
+        if act.use_step_id:
+            ctx = ctx + self.stepid_embedding(batch["step_ids"].long())
+        B = len(batch["npoints_in_batch"])
+        return {"coord": batch["pc_fts"][:, :3], "grid_size": act.voxel_size, "offset": batch["offset"],
+                "feat": batch["pc_fts"], "stem_context": ctx.contiguous(), "counts": list(batch["npoints_in_batch"]),
+                "context_counts": [1] * B}
+
+    def forward(self, batch, compute_loss=False, **kwargs):
+        if self.act_storage == "bf16":
+            raise NotImplementedError("SimplePolicyPTV3Concat: act_storage='bf16' is not built (fp32 activations only)")
+        mode = self.gemm_precision or ops.get_gemm_precision()
+        if mode != "fp32":  # the context stem is exact fp32, as is the patch attention without q/k LayerNorm
+            raise NotImplementedError(f"SimplePolicyPTV3Concat is built for gemm_precision None / 'fp32' only, got {mode!r}")
+        return SimplePolicyPTV3CA.forward(self, batch, compute_loss, **kwargs)
+
+
 def _factory():
     from .motion_planner import MotionPlannerPTV3AdaNorm, MotionPlannerPTV3CA
     return {"SimplePolicyPTV3CA": SimplePolicyPTV3CA, "MotionPlannerPTV3CA": MotionPlannerPTV3CA,
-            "SimplePolicyPTV3AdaNorm": SimplePolicyPTV3AdaNorm, "MotionPlannerPTV3AdaNorm": MotionPlannerPTV3AdaNorm}
+            "SimplePolicyPTV3AdaNorm": SimplePolicyPTV3AdaNorm, "MotionPlannerPTV3AdaNorm": MotionPlannerPTV3AdaNorm,
+            "SimplePolicyPTV3Concat": SimplePolicyPTV3Concat}
 
 
 class _Factory(dict):
@@ -434,4 +486,5 @@ class _Factory(dict):
         return dict.__getitem__(self, k)
 
 
-MODEL_FACTORY = _Factory({"SimplePolicyPTV3CA": SimplePolicyPTV3CA, "SimplePolicyPTV3AdaNorm": SimplePolicyPTV3AdaNorm})
+MODEL_FACTORY = _Factory({"SimplePolicyPTV3CA": SimplePolicyPTV3CA, "SimplePolicyPTV3AdaNorm": SimplePolicyPTV3AdaNorm,
+                          "SimplePolicyPTV3Concat": SimplePolicyPTV3Concat})
