@@ -3,7 +3,7 @@
 The reference repeats the context vector of a cloud — txt_fc(txt) (+ pose) (+ step) — over the cloud's points and concatenates it
 to pc_fts (:457-461); the backbone is then a plain PointTransformerV3 (PointTransformerV3/model.py:864-1100, no cross attention,
 no adaptive norm) whose 5^3 stem convolution (:844-853) has `c_pc + context_channels` input columns.  All but c_pc of them are
-constant over a cloud, and SubMConv3d is linear in its input columns (as adanorm.AdaStemGroupsFn already uses), so with
+constant over a cloud, and SubMConv3d is linear in its input columns (as adanorm.StemGroupsFn already uses), so with
 P_b[t] = W_ctx[:, t, :] ctx_b for the 125 taps t
 
     conv(W, [pc | ctx_b(i)])_i = conv(W_pc, pc)_i + sum over the taps t with nbr125[t][i] >= 0 of P_b(i)[t]
@@ -13,16 +13,16 @@ neighbour table and a [B, 125, cout] table that one small dense product makes: c
 (c_pc + 256) x cout multiply-adds, and the [N, c_pc + 256] input never exists (csrc/ctx_stem.hip: lotus_ctx_taps_fwd / _bwd).
 
 PointTransformerV3Plain is ptv3.PointTransformerV3CA's skeleton with the hooks overridden: every stage a chain of Blocks, the stem
-above, plain BatchNorm pooling / unpooling.  qk_norm True runs ptv3.Block.run (the composites) as it is; qk_norm False runs the
-attention sub-block per launch (PlainSelfAttnFn) — LayerNorm, qkv, patch attention without q/k LayerNorm, proj — as
-adanorm.AdaSelfAttnFn does around its PDNorm.  fp32 activation storage only.
+above, plain BatchNorm pooling / unpooling.  Either way the blocks run ptv3.Block.run: with qk_norm True the composites as they
+are; with qk_norm False ops.SelfAttnFn runs per launch — LayerNorm, qkv, patch attention without q/k LayerNorm, proj — and no
+hand-over is made.  fp32 activation storage only.
 """
 import torch
 import torch.nn as nn
 
 from . import ops
 from ._capi import call, query, WS
-from .ops import ACT_GELU, _fwd, _joined, mix_seed
+from .ops import ACT_GELU, _fwd, _joined
 from .ptv3 import Block, PointTransformerV3CA, _Attn
 
 _WS_SLOT = 6  # workspace slot of the dP chunk partials (main stream)
@@ -92,29 +92,6 @@ class CtxStemFn(torch.autograd.Function):
         return None, dcvec, dw_pc, dw_ctx, dg, db, None, None, None, None
 
 
-class PlainSelfAttnFn(torch.autograd.Function):
-    """y = x + DropPath(drop(proj(PatchAttention(qkv(LN(x))))))   (model.py:664-668) with attn.q_norm = attn.k_norm = nn.Identity
-    (qk_norm False), per launch: ops.selfattn_branch_fwd / _bwd between the plain LayerNorm's passes."""
-
-    @_fwd
-    def forward(ctx, x, g, b, wqkv, bqkv, wp, bp, lvl, H, drop_p, seed, attn_p, dpath):
-        n, mean, rstd = ops.ln_fwd(x, g, b)
-        y, qkv, att, lse = ops.selfattn_branch_fwd(n, x, wqkv, bqkv, None, None, wp, bp, lvl, H, drop_p, seed, attn_p, dpath)
-        ctx.meta = (lvl, H, drop_p, seed, attn_p, float(dpath))
-        ctx.save_for_backward(x, g, wqkv, wp, n, qkv, att, lse, mean, rstd)
-        return y
-
-    @_joined
-    def backward(ctx, dy):
-        x, g, wqkv, wp, n, qkv, att, lse, mean, rstd = ctx.saved_tensors
-        lvl, H, p, seed, attn_p, dpath = ctx.meta
-        dy = dy.contiguous()
-        dn, dwqkv, dbqkv, _, _, _, _, dwp, dbp = ops.selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, None, None, wp, lvl, H, p, seed,
-                                                                         attn_p, dpath, None)
-        dx, dg, db = ops.ln_bwd(dn, x, mean, rstd, g, add=dy)
-        return (dx, dg, db, dwqkv, dbqkv, dwp, dbp) + (None,) * 6
-
-
 class PlainBlock(Block):
     """model.py:586-680; qk_norm False registers attn.q_norm / k_norm as nn.Identity (model.py:393-394): no state entries."""
 
@@ -122,17 +99,6 @@ class PlainBlock(Block):
         super().__init__(c, h, mlp_ratio)
         if not qk_norm:
             self.attn = _Attn(c, h, False)
-
-    def run_plain(self, x, xs, lvl, drop_p, seed, attn_p=0.0, wt=None, dpath=0.0):
-        """Block.run without q/k LayerNorm: the same seeds per sub-block, the attention sub-block per launch."""
-        c0, c1, c2 = self.cpe[0], self.cpe[1], self.cpe[2]
-        x = ops.CpeFn.apply(x, xs, c0.weight, c0.bias, c1.weight, c1.bias, c2.weight, c2.bias, lvl, wt)
-        a, n1 = self.attn, self.norm1[0]
-        x = PlainSelfAttnFn.apply(x, n1.weight, n1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias, lvl, self.num_heads,
-                                  drop_p, seed, attn_p, dpath)
-        m, n2 = self.mlp[0], self.norm2[0]
-        return ops.FfnFn.apply(x, n2.weight, n2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, drop_p, mix_seed(seed, 2),
-                               None, None, dpath)
 
 
 class PointTransformerV3Plain(PointTransformerV3CA):
@@ -203,6 +169,4 @@ class PointTransformerV3Plain(PointTransformerV3CA):
 
     def _run_depth(self, fw, stage, i, x, xs, lvl_o, lvl, si, dpath):
         blk = getattr(stage, f"block{i}")
-        if self.qk_norm:
-            return blk.run(x, xs, lvl_o, fw.p, si, fw.pa, fw.packs[blk], dpath)[0]
-        return blk.run_plain(x, xs, lvl_o, fw.p, si, fw.pa, fw.packs[blk], dpath)
+        return blk.run(x, xs, lvl_o, fw.p, si, fw.pa, fw.packs[blk], dpath)[0]

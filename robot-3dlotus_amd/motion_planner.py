@@ -248,7 +248,7 @@ class MotionPlannerPTV3AdaNorm(MotionPlannerPTV3CA):
     def prepare_ptv3_batch(self, batch):
         """motion_planner_ptv3.py:190-222: feat = [pc_fts | label embedding], context = one vector per cloud (txt_fc reduced by
         'mean' — one token per cloud — or 'attn', plus the pose embedding).  The stem convolution is linear in its input
-        columns, so its two column groups are convolved separately (adanorm.AdaStemGroupsFn): the point features with
+        columns, so its two column groups are convolved separately (adanorm.StemGroupsFn): the point features with
         W[..., :c_pc], the one-hot label with W[..., c_pc:] E^T (the embedding folded into the weight as MotionPlannerPTV3CA
         does); autograd carries both weight gradients back into stem.conv.weight and the embedding table."""
         from .adanorm import cloud_context

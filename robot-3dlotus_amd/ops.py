@@ -513,12 +513,24 @@ def linear_wgrad(dy, x, need_bias=True, prec=None, into=None):
     return dw, db
 
 
-def ln_fwd(x, g, b, res=None, eps=1e-5, save=True):
+_ADA_WS_SLOT = 6  # workspace slot of the adaptive norms' (P, Q) partials (main stream)
+
+
+def _n_clouds(lvl):
+    return len(lvl.counts)
+
+
+def ln_fwd(x, g, b, res=None, eps=1e-5, save=True, mod=None, lvl=None):
+    """LN(x) g + b (+ res).  mod = [B, 2C] (row stride free) of [shift | scale], one row per cloud of `lvl`: the adaptive PDNorm
+    (model.py:257-303), (LN(x) g + b) (1 + scale_b) + shift_b (+ res); None: the plain LayerNorm."""
     M, C = x.shape
     y = torch.empty_like(x)
     mean = torch.empty(M, dtype=torch.float32, device=x.device) if save else None
     rstd = torch.empty(M, dtype=torch.float32, device=x.device) if save else None
-    call("lotus_layernorm_fwd", x, res, g, b, y, mean, rstd, M, C, float(eps))
+    if mod is None:
+        call("lotus_layernorm_fwd", x, res, g, b, y, mean, rstd, M, C, float(eps))
+    else:
+        call("lotus_adaln_fwd", x, res, g, b, mod, mod.stride(0), lvl.off, _n_clouds(lvl), y, mean, rstd, M, C, float(eps))
     return y, mean, rstd
 
 
@@ -558,11 +570,19 @@ def _masked(dy, p, seed, hand):
     return dropout(dy, p, seed)
 
 
-def ln_bwd(dy, x, mean, rstd, g, add=None, hand=None):
+def ln_bwd(dy, x, mean, rstd, g, add=None, hand=None, b=None, mod=None, dmod=None, lvl=None):
+    """-> dx (+ add), dgamma, dbeta.  With `mod` (see ln_fwd; needs b) d mod is written into `dmod` ([B, 2C] view) by the one
+    adaptive launch, which takes no hand-over."""
     M, C = x.shape
     dx = torch.empty_like(x)
     dg = torch.empty(C, dtype=torch.float32, device=x.device)
     db = torch.empty(C, dtype=torch.float32, device=x.device)
+    if mod is not None:
+        B = _n_clouds(lvl)
+        ws = WS.get(query("lotus_adanorm_workspace", M, B, C), x.device, slot=_ADA_WS_SLOT)
+        call("lotus_adaln_bwd", dy, x, mean, rstd, g, b, mod, mod.stride(0), lvl.off, B, add, dx, dg, db, dmod, dmod.stride(0), M, C,
+             ws, ws.numel())
+        return dx, dg, db
     dz, dp, dseed = Handoff.offer(hand, dx)
     nbytes = query("lotus_layernorm_bwd_workspace", M, C)
     if _side() is None:
@@ -831,23 +851,42 @@ def _bn_stats(x, sums):
     call("lotus_batchnorm_stats", x, sums, M, C, ws, ws.numel())
 
 
-def _bn_finish(x, sums, g, b, rmean, rvar, training, act, momentum, eps):
+def _bn_apply(x, mean, invstd, g, b, act, mod=None, lvl=None):
+    M, C = x.shape
+    y = torch.empty_like(x)
+    if mod is None:
+        call("lotus_batchnorm_apply", x, mean, invstd, g, b, y, M, C, act)
+    else:
+        call("lotus_adabn_apply", x, mean, invstd, g, b, mod, mod.stride(0), lvl.off, _n_clouds(lvl), y, M, C, act)
+    return y
+
+
+def _bn_apply_sums(x, sums, g, b, rmean, rvar, act, momentum=BN_MOMENTUM, eps=BN_EPS, mod=None, lvl=None):
+    """statistics -> (message) -> apply: the apply pass finishes mean / invstd / running averages from the (all-reduced) sums
+    itself (SyncBatchNorm forward: one launch less between the all-reduce and the consumer)."""
     M, C = x.shape
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-    if training and x.is_cuda:
-        # statistics -> (message) -> apply: the apply pass finishes mean / invstd / running averages itself (SyncBatchNorm
-        # forward: one launch less between the all-reduce and the consumer)
-        y = torch.empty_like(x)
+    y = torch.empty_like(x)
+    if mod is None:
         call("lotus_batchnorm_apply_sums", x, sums, g, b, y, mean, invstd, rmean, rvar, M, C, act, float(eps), float(momentum))
-        return y, mean, invstd
+    else:
+        call("lotus_adabn_apply_sums", x, sums, g, b, mod, mod.stride(0), lvl.off, _n_clouds(lvl), y, mean, invstd, rmean, rvar,
+             M, C, act, float(eps), float(momentum))
+    return y, mean, invstd
+
+
+def _bn_finish(x, sums, g, b, rmean, rvar, training, act, momentum, eps, mod=None, lvl=None):
+    if training and x.is_cuda:
+        return _bn_apply_sums(x, sums, g, b, rmean, rvar, act, momentum, eps, mod, lvl)
+    C = x.shape[1]
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    invstd = torch.empty(C, dtype=torch.float32, device=x.device)
     if training:
         call("lotus_batchnorm_finalize", sums, mean, invstd, rmean, rvar, C, float(eps), float(momentum))
     else:
         call("lotus_batchnorm_eval_stats", rmean, rvar, mean, invstd, C, float(eps))
-    y = torch.empty_like(x)
-    call("lotus_batchnorm_apply", x, mean, invstd, g, b, y, M, C, act)
-    return y, mean, invstd
+    return _bn_apply(x, mean, invstd, g, b, act, mod, lvl), mean, invstd
 
 
 _BN_FUSED = True  # one-launch BatchNorm statistics (two-level last-arrival reduction); False: the partials + reduce launches
@@ -862,7 +901,10 @@ def _bn_counter(dev):
     return _counters(dev).data_ptr() + _BN_CNT_OFF
 
 
-def bn_fwd(x, g, b, rmean, rvar, training, act, momentum=BN_MOMENTUM, eps=BN_EPS):
+def bn_fwd(x, g, b, rmean, rvar, training, act, momentum=BN_MOMENTUM, eps=BN_EPS, mod=None, lvl=None):
+    """act(BN(x) g + b): batch statistics (+ running-average update) in training, running ones in eval; with a statistics hook
+    (BnState.reduce: SyncBatchNorm) the training pass is statistics -> one fp64 message (sum x, sum x^2, rows) -> apply.
+    mod / lvl as in ln_fwd: act((BN(x) g + b) (1 + scale_b) + shift_b) — the same statistics, the adaptive apply entry."""
     sums = None
     if training and _BN_FUSED and BnState.reduce is None and x.shape[0] > 0:
         # local batch statistics: statistics, their reduction, mean / invstd and the running averages in ONE launch
@@ -873,35 +915,44 @@ def bn_fwd(x, g, b, rmean, rvar, training, act, momentum=BN_MOMENTUM, eps=BN_EPS
         ws = _ws(query("lotus_batchnorm_workspace", M, C), x.device)
         call("lotus_batchnorm_stats_fused", x, sums, mean, invstd, rmean, rvar, M, C, float(eps), float(momentum), ws, ws.numel(),
              _bn_counter(x.device))
-        y = torch.empty_like(x)
-        call("lotus_batchnorm_apply", x, mean, invstd, g, b, y, M, C, act)
-        return y, mean, invstd
+        return _bn_apply(x, mean, invstd, g, b, act, mod, lvl), mean, invstd
     if training:
         sums = torch.empty(2 * x.shape[1] + 1, dtype=torch.float64, device=x.device)
         _bn_stats(x, sums)
         if BnState.reduce is not None:
             BnState.reduce(sums)
-    return _bn_finish(x, sums, g, b, rmean, rvar, training, act, momentum, eps)
+    return _bn_finish(x, sums, g, b, rmean, rvar, training, act, momentum, eps, mod, lvl)
 
 
 def bn_fwd_pair(xa, pa, xb, pb, training, act, momentum=BN_MOMENTUM, eps=BN_EPS):
     """Two independent BatchNorms (the two branches of SerializedUnpooling) with ONE statistics message when
-    SyncBatchNorm is on: the all-reduces are latency-bound, 26 -> 18 per step.  pa / pb = (g, b, rmean, rvar)."""
+    SyncBatchNorm is on: the all-reduces are latency-bound, 26 -> 18 per step.  pa / pb = (g, b, rmean, rvar[, mod, lvl])."""
     if not training or BnState.reduce is None:
-        return bn_fwd(xa, *pa, training, act, momentum, eps), bn_fwd(xb, *pb, training, act, momentum, eps)
+        return (bn_fwd(xa, *pa[:4], training, act, momentum, eps, *pa[4:]),
+                bn_fwd(xb, *pb[:4], training, act, momentum, eps, *pb[4:]))
     na, nb_ = 2 * xa.shape[1] + 1, 2 * xb.shape[1] + 1
     sums = torch.empty(na + nb_, dtype=torch.float64, device=xa.device)
     _bn_stats(xa, sums[:na])
     _bn_stats(xb, sums[na:])
     BnState.reduce(sums)
-    return (_bn_finish(xa, sums[:na], *pa, training, act, momentum, eps),
-            _bn_finish(xb, sums[na:], *pb, training, act, momentum, eps))
+    return (_bn_finish(xa, sums[:na], *pa[:4], training, act, momentum, eps, *pa[4:]),
+            _bn_finish(xb, sums[na:], *pb[:4], training, act, momentum, eps, *pb[4:]))
 
 
-def _bn_bwd_stats(dy, x, mean, invstd, g, b, act, sums, want_params=False):
+def _bn_bwd_stats(dy, x, mean, invstd, g, b, act, sums, want_params=False, mod=None, dmod=None, lvl=None):
     """sums = (sum dz, sum dz * xhat, M) of the local rows; want_params: also (dgamma, dbeta) as fp32 vectors taken from those
-    LOCAL sums (SyncBatchNorm: before the all-reduce overwrites them) — written by the statistics kernel itself on the GPU."""
+    LOCAL sums (SyncBatchNorm: before the all-reduce overwrites them) — written by the statistics kernel itself on the GPU.
+    With `mod` (the split backward only): dgamma, dbeta (local, as above), d mod into `dmod` and the fp64 message
+    sums = (gamma dbeta, gamma dgamma, rows) from the adaptive partial pass and its fixed-order reduction."""
     M, C = x.shape
+    if mod is not None:
+        B = _n_clouds(lvl)
+        dg = torch.empty(C, dtype=torch.float32, device=x.device)
+        db = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws = WS.get(query("lotus_adanorm_workspace", M, B, C), x.device, slot=_ADA_WS_SLOT)
+        call("lotus_adabn_bwd_stats", dy, x, mean, invstd, g, b, mod, mod.stride(0), lvl.off, B, dg, db, dmod, dmod.stride(0), sums,
+             M, C, act, ws, ws.numel())
+        return dg, db
     ws = _ws(query("lotus_batchnorm_workspace", M, C), x.device)
     if want_params and _BN_FUSED and M > 0 and x.is_cuda:
         dg = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -917,12 +968,15 @@ def _bn_bwd_stats(dy, x, mean, invstd, g, b, act, sums, want_params=False):
         call("lotus_batchnorm_bwd_stats", dy, x, mean, invstd, g, b, sums, M, C, act, ws, ws.numel())
 
 
-def _bn_bwd_apply(dy, x, mean, invstd, g, b, training, act, sums, reduced):
+def _bn_bwd_apply(dy, x, mean, invstd, g, b, training, act, sums, reduced, mod=None, dmod=None, lvl=None):
     # dgamma / dbeta are the LOCAL sums (gradient averaging across ranks is the reducer's job);
     # dx uses the statistics of the whole (all-rank) batch
     M, C = x.shape
     dx = torch.empty_like(x)
-    if reduced is not None:  # (dg, db) were taken from the local sums before the all-reduce
+    if mod is not None:  # (the split backward: `reduced` and d mod come from _bn_bwd_stats)
+        dg, db = reduced
+        call("lotus_adabn_bwd_apply_sums", dy, x, mean, invstd, g, b, mod, mod.stride(0), lvl.off, _n_clouds(lvl), sums, dx, M, C, act)
+    elif reduced is not None:  # (dg, db) were taken from the local sums before the all-reduce
         dg, db = reduced
         call("lotus_batchnorm_bwd_apply", dy, x, mean, invstd, g, b, sums, dx, None, None, M, C, act, 1, 0)
     else:  # local statistics: the apply kernel writes the parameter gradients itself
@@ -933,30 +987,46 @@ def _bn_bwd_apply(dy, x, mean, invstd, g, b, training, act, sums, reduced):
     return dx, dg, db
 
 
-def bn_bwd(dy, x, mean, invstd, g, b, training, act):
-    C = x.shape[1]
+def bn_bwd(dy, x, mean, invstd, g, b, training, act, mod=None, dmod=None, lvl=None):
+    """-> dx, dgamma, dbeta (+ d mod into `dmod`): statistics -> (one fp64 message when SyncBatchNorm is on) -> apply; the
+    adaptive norm with local statistics is one entry point."""
+    M, C = x.shape
+    split = training and BnState.reduce is not None
+    if mod is not None and not split:
+        B = _n_clouds(lvl)
+        dx = torch.empty_like(x)
+        dg = torch.empty(C, dtype=torch.float32, device=x.device)
+        db = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws = WS.get(query("lotus_adanorm_workspace", M, B, C), x.device, slot=_ADA_WS_SLOT)
+        call("lotus_adabn_bwd", dy, x, mean, invstd, g, b, mod, mod.stride(0), lvl.off, B, dx, dg, db, dmod, dmod.stride(0), M, C, act,
+             1 if training else 0, ws, ws.numel())
+        return dx, dg, db
     sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
-    reduced = None
-    if training and BnState.reduce is not None:
-        reduced = _bn_bwd_stats(dy, x, mean, invstd, g, b, act, sums, want_params=True)
+    reduced = _bn_bwd_stats(dy, x, mean, invstd, g, b, act, sums, split, mod, dmod, lvl)
+    if split:
         BnState.reduce(sums)
-    else:
-        _bn_bwd_stats(dy, x, mean, invstd, g, b, act, sums)
-    return _bn_bwd_apply(dy, x, mean, invstd, g, b, training, act, sums, reduced)
+    return _bn_bwd_apply(dy, x, mean, invstd, g, b, training, act, sums, reduced, mod, dmod, lvl)
 
 
 def bn_bwd_pair(a, bb, training, act):
-    """Backward of bn_fwd_pair: a / bb = (dy, x, mean, invstd, g, b); one statistics message for both."""
+    """Backward of bn_fwd_pair: a / bb = (dy, x, mean, invstd, g, b[, mod, dmod, lvl]); one statistics message for both."""
     if not training or BnState.reduce is None:
-        return bn_bwd(*a, training, act), bn_bwd(*bb, training, act)
+        return bn_bwd(*a[:6], training, act, *a[6:]), bn_bwd(*bb[:6], training, act, *bb[6:])
     Ca, Cb = a[1].shape[1], bb[1].shape[1]
     na = 2 * Ca + 1
     sums = torch.empty(na + 2 * Cb + 1, dtype=torch.float64, device=a[1].device)
     sa, sb = sums[:na], sums[na:]
-    ra = _bn_bwd_stats(*a, act, sa, want_params=True)
-    rb = _bn_bwd_stats(*bb, act, sb, want_params=True)
+    ra = _bn_bwd_stats(*a[:6], act, sa, True, *a[6:])
+    rb = _bn_bwd_stats(*bb[:6], act, sb, True, *bb[6:])
     BnState.reduce(sums)
-    return _bn_bwd_apply(*a, training, act, sa, ra), _bn_bwd_apply(*bb, training, act, sb, rb)
+    return _bn_bwd_apply(*a[:6], training, act, sa, ra, *a[6:]), _bn_bwd_apply(*bb[:6], training, act, sb, rb, *bb[6:])
+
+
+def silu(x, dy=None):
+    """SiLU(x), or dy SiLU'(x) when dy is given."""
+    y = torch.empty_like(x)
+    call("lotus_ada_silu", x, dy, y, x.numel())
+    return y
 
 
 def _qk_norms(qn, kn):
@@ -1118,9 +1188,14 @@ def _side_ctx(dev, ws_side_bytes, reads, rows=0):
 
 
 # ------------------------------------------------------------------------------------ sub-blocks
-# Per-launch bodies of the three Block sub-blocks WITHOUT their norm: the part the plain-LayerNorm nodes below (their
-# per-launch branches) and the PDNorm nodes of adanorm.py share.  The caller passes the weights it uses (bf16 shadows here, the
-# parameters there) and runs its own norm forward / backward around them.
+# Every node that ends or begins in a norm takes trailing `mod = None, bank = None, j = 0`: the [B, 2C] modulation slice of an
+# adaptive PDNorm (adanorm.py; None = the plain norm), and the bank whose grad_slice(j) the norm's backward writes d mod into
+# (returned as the gradient of `mod`).  The composite (one C call) branches are plain LayerNorm with q/k norm only; with `mod`,
+# without q/k norm, with DropPath or with composites off a node runs per launch: its norm, then the bodies below.
+def _dmod(mod, site):
+    return None if mod is None else site[0].grad_slice(site[1])
+
+
 def cpe_branch_fwd(xs, cw, cb, lw, lb, lvl, wt):
     """-> (c, l) = SubMConv3d_3(xs), Linear(c): the input of the sub-block's norm, and what its backward needs."""
     c = conv_fwd(xs, cw, cb, lvl.nbr27, lvl.order[0], w_t=wt, tap_plan=lvl.tap_plan)
@@ -1205,15 +1280,16 @@ class CpeFn(torch.autograd.Function):
     stale proj_skip branch (SURVEY.md Trap 3), hence two tensor inputs."""
 
     @_fwd
-    def forward(ctx, x, xs, cw, cb, lw, lb, g, b, lvl, wt=None):
+    def forward(ctx, x, xs, cw, cb, lw, lb, g, b, lvl, wt=None, mod=None, bank=None, j=0):
         same = xs is x
         if wt is None:
             wt = conv_weight_t(cw)
-        ctx.lvl, ctx.same = lvl, same
+        ctx.lvl, ctx.same, ctx.site = lvl, same, (bank, j)
         n_, C = x.shape
         (lwk,), pc = _wk(lw)
         ctx.wk, ctx.pc = (lwk,), pc
-        ctx.comp = composites_enabled() and C % 64 == 0 and (C == 64 or C % 128 == 0) and cw.shape[0] == C and cw.shape[-1] == C
+        ctx.comp = (mod is None and composites_enabled() and C % 64 == 0 and (C == 64 or C % 128 == 0) and cw.shape[0] == C
+                    and cw.shape[-1] == C)
         if ctx.comp:
             n_saved, _, _, ws_main, _, ws_conv = _sizes("cpe", n_, C)
             saved = torch.empty(n_saved, dtype=torch.float32, device=x.device)
@@ -1225,8 +1301,8 @@ class CpeFn(torch.autograd.Function):
             ctx.save_for_backward(xs, cw, lw, g, saved, wt)
             return y
         c, l = cpe_branch_fwd(xs, cw, cb, lwk, lb, lvl, wt)
-        y, mean, rstd = ln_fwd(l, g, b, res=x)
-        ctx.save_for_backward(xs, cw, lw, g, c, l, mean, rstd, wt)
+        y, mean, rstd = ln_fwd(l, g, b, res=x, mod=mod, lvl=lvl)
+        ctx.save_for_backward(xs, cw, lw, g, c, l, mean, rstd, wt, b, mod)
         return y
 
     @_joined
@@ -1244,17 +1320,19 @@ class CpeFn(torch.autograd.Function):
             _capi.call_raw("lotus_cpe_bwd", dy, xs, cw, wt, ctx.wk[0], g, saved, dxc, 1 if ctx.same else 0, grads, tmp, lvl.nbr27,
                            lvl.order[0], lvl.tap_plan, lvl.code[0], lvl.n_dup, n_, C, ctx.pc, wsm, wsm.numel(), wc, wc.numel(), wss,
                            wss_bytes, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
-            return ((dxc, None) if ctx.same else (dy, dxc)) + _grad_views(grads, "cpe", C, cshape=cw.shape) + (None, None)
-        xs, cw, lw, g, c, l, mean, rstd, wt = ctx.saved_tensors
-        dl, dg, db = ln_bwd(dy, l, mean, rstd, g)
-        return cpe_branch_bwd(dl, dy, xs, cw, ctx.wk[0], c, lvl, wt, ctx.same) + (dg, db, None, None)
+            return ((dxc, None) if ctx.same else (dy, dxc)) + _grad_views(grads, "cpe", C, cshape=cw.shape) + (None,) * 5
+        xs, cw, lw, g, c, l, mean, rstd, wt, b, mod = ctx.saved_tensors
+        dmod = _dmod(mod, ctx.site)
+        dl, dg, db = ln_bwd(dy, l, mean, rstd, g, b=b, mod=mod, dmod=dmod, lvl=lvl)
+        return cpe_branch_bwd(dl, dy, xs, cw, ctx.wk[0], c, lvl, wt, ctx.same) + (dg, db, None, None, dmod, None, None)
 
 
 class FfnFn(torch.autograd.Function):
     """y = x + drop(fc2(drop(GELU(fc1(LN(x))))))   (MLP, model.py:577-583; pre-norm residual)."""
 
     @_fwd
-    def forward(ctx, x, g, b, w1, b1, w2, b2, drop_p, seed, hand_in=None, hand_out=None, dpath=0.0):
+    def forward(ctx, x, g, b, w1, b1, w2, b2, drop_p, seed, hand_in=None, hand_out=None, dpath=0.0, lvl=None, mod=None, bank=None,
+                j=0):
         # dpath > 0: DropPath on the branch (Block.mlp only, training only; model.py:672) — its own elementwise pass, the
         # per-launch path, no hand-over of a pre-masked gradient (the published models train with drop_path 0)
         ctx.drop = (drop_p, seed)
@@ -1264,7 +1342,8 @@ class FfnFn(torch.autograd.Function):
         ctx.hands = (hand_in, hand_out)
         if hand_in is not None:
             hand_in.arm(drop_p, mix_seed(seed, 1))
-        ctx.comp = composites_enabled() and x.shape[1] % 4 == 0 and dpath == 0.0
+        ctx.lvl, ctx.site = lvl, (bank, j)  # (lvl: the level whose clouds modulate, with `mod` only)
+        ctx.comp = mod is None and composites_enabled() and x.shape[1] % 4 == 0 and dpath == 0.0
         (w1k, w2k), pc = _wk(w1, w2)
         ctx.wk, ctx.pc = (w1k, w2k), pc
         if ctx.comp:
@@ -1278,9 +1357,9 @@ class FfnFn(torch.autograd.Function):
                            mix_seed(seed, 1), pc, ws, ws.numel(), _counters(x.device), _capi.stream_ptr())
             ctx.save_for_backward(x, g, w1, w2, saved)
             return y
-        n, mean, rstd = ln_fwd(x, g, b)
+        n, mean, rstd = ln_fwd(x, g, b, mod=mod, lvl=lvl)
         y, a, hpre = ffn_branch_fwd(n, x, w1k, b1, w2k, b2, drop_p, seed, dpath)
-        ctx.save_for_backward(x, g, w1, w2, n, hpre, a, mean, rstd)
+        ctx.save_for_backward(x, g, w1, w2, n, hpre, a, mean, rstd, b, mod)
         return y
 
     @_joined
@@ -1300,18 +1379,21 @@ class FfnFn(torch.autograd.Function):
             _capi.call_raw("lotus_ffn_bwd", dy, dz_in, x, g, ctx.wk[0], ctx.wk[1], saved, dx, dz_out, po, so, grads, tmp, M, C, Hd, float(p),
                            int(seed), mix_seed(seed, 1), ctx.pc, wsm, wsm.numel(), wss, wss_bytes, _counters(dev), cs, _LINK, 0,
                            _capi.stream_ptr(), side)
-            return (dx,) + _grad_views(grads, "ffn", C, Hd=Hd) + (None,) * 5
-        x, g, w1, w2, n, hpre, a, mean, rstd = ctx.saved_tensors
+            return (dx,) + _grad_views(grads, "ffn", C, Hd=Hd) + (None,) * 9
+        x, g, w1, w2, n, hpre, a, mean, rstd, b, mod = ctx.saved_tensors
         dn, dw1, db1, dw2, db2 = ffn_branch_bwd(dy, n, hpre, a, ctx.wk[0], ctx.wk[1], p, seed, ctx.dpath, hand_in)
-        dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy, hand=hand_out)
-        return dx, dg, db, dw1, db1, dw2, db2, None, None, None, None, None
+        dmod = _dmod(mod, ctx.site)
+        dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy, hand=hand_out, b=b, mod=mod, dmod=dmod, lvl=ctx.lvl)
+        return (dx, dg, db, dw1, db1, dw2, db2) + (None,) * 6 + (dmod, None, None)
 
 
 class SelfAttnFn(torch.autograd.Function):
     """y = x + drop(proj(PatchAttention(qkv(LN(x)))))   (SerializedAttention flash path)."""
 
     @_fwd
-    def forward(ctx, x, g, b, wqkv, bqkv, qnw, qnb, knw, knb, wp, bp, lvl, H, drop_p, seed, attn_p=0.0, hand_in=None, dpath=0.0):
+    def forward(ctx, x, g, b, wqkv, bqkv, qnw, qnb, knw, knb, wp, bp, lvl, H, drop_p, seed, attn_p=0.0, hand_in=None, dpath=0.0,
+                mod=None, bank=None, j=0):
+        """qnw = qnb = knw = knb = None: a block without q_norm / k_norm (qk_norm False)."""
         N, C = x.shape
         d = C // H
         ctx.meta = (lvl, H, d, drop_p, seed, attn_p)
@@ -1321,7 +1403,8 @@ class SelfAttnFn(torch.autograd.Function):
         ctx.hand_in = hand_in
         if hand_in is not None:
             hand_in.arm(drop_p, seed)
-        ctx.comp = composites_enabled() and C % 4 == 0 and dpath == 0.0
+        ctx.site = (bank, j)
+        ctx.comp = mod is None and qnw is not None and composites_enabled() and C % 4 == 0 and dpath == 0.0
         (wqkvk, wpk), pc = _wk(wqkv, wp)
         ctx.wk, ctx.pc = (wqkvk, wpk), pc
         if ctx.comp:
@@ -1334,9 +1417,10 @@ class SelfAttnFn(torch.autograd.Function):
                            float(attn_p), mix_seed(seed, 1), pc, ws, ws.numel(), _counters(x.device), _capi.stream_ptr())
             ctx.save_for_backward(x, g, wqkv, qnw, qnb, knw, knb, wp, saved)
             return y
-        n, mean, rstd = ln_fwd(x, g, b)
-        y, qkv, att, lse = selfattn_branch_fwd(n, x, wqkvk, bqkv, (qnw, qnb), (knw, knb), wpk, bp, lvl, H, drop_p, seed, attn_p, dpath)
-        ctx.save_for_backward(x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd)
+        n, mean, rstd = ln_fwd(x, g, b, mod=mod, lvl=lvl)
+        qn, kn = ((qnw, qnb), (knw, knb)) if qnw is not None else (None, None)
+        y, qkv, att, lse = selfattn_branch_fwd(n, x, wqkvk, bqkv, qn, kn, wpk, bp, lvl, H, drop_p, seed, attn_p, dpath)
+        ctx.save_for_backward(x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd, b, mod)
         return y
 
     @_joined
@@ -1355,12 +1439,14 @@ class SelfAttnFn(torch.autograd.Function):
                            lvl.owner, lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, lvl.kext, lvl.ext_pos, lvl.n_extra, lvl.npad,
                            N, C, H, float(d ** -0.5), float(p), int(seed), float(attn_p), mix_seed(seed, 1), ctx.pc, wsm, wsm.numel(),
                            wss, wss_bytes, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
-            return (dx,) + _grad_views(grads, "self", C, H) + (None,) * 7
-        x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd = ctx.saved_tensors
-        dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp = selfattn_branch_bwd(dy, n, qkv, att, lse, ctx.wk[0], (qnw, qnb), (knw, knb),
-                                                                         ctx.wk[1], lvl, H, p, seed, attn_p, ctx.dpath, ctx.hand_in)
-        dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy)
-        return dx, dg, db, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, None, None, None, None, None, None, None
+            return (dx,) + _grad_views(grads, "self", C, H) + (None,) * 10
+        x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd, b, mod = ctx.saved_tensors
+        qn, kn = ((qnw, qnb), (knw, knb)) if qnw is not None else (None, None)
+        dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp = selfattn_branch_bwd(dy, n, qkv, att, lse, ctx.wk[0], qn, kn, ctx.wk[1], lvl, H,
+                                                                         p, seed, attn_p, ctx.dpath, ctx.hand_in)
+        dmod = _dmod(mod, ctx.site)
+        dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy, b=b, mod=mod, dmod=dmod, lvl=lvl)
+        return (dx, dg, db, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp) + (None,) * 7 + (dmod, None, None)
 
 
 class CrossAttnFn(torch.autograd.Function):
@@ -1718,31 +1804,33 @@ class StemFn(torch.autograd.Function):
     """Embedding: GELU(BN(SubMConv3d_5(x)))   (model.py:844-861; conv has no bias)."""
 
     @_fwd
-    def forward(ctx, x, cw, g, b, rmean, rvar, lvl, training):
+    def forward(ctx, x, cw, g, b, rmean, rvar, lvl, training, mod=None, bank=None, j=0):
         c = conv_fwd(x, cw, None, lvl.nbr125, lvl.order[0])
-        y, mean, invstd = bn_fwd(c, g, b, rmean, rvar, training, ACT_GELU)
-        ctx.save_for_backward(x, cw, g, b, c, mean, invstd)
-        ctx.meta = (lvl, training)
+        y, mean, invstd = bn_fwd(c, g, b, rmean, rvar, training, ACT_GELU, mod=mod, lvl=lvl)
+        ctx.save_for_backward(x, cw, g, b, c, mean, invstd, mod)
+        ctx.meta = (lvl, training, (bank, j))
         return y
 
     @_joined
     def backward(ctx, dy):
-        x, cw, g, b, c, mean, invstd = ctx.saved_tensors
-        lvl, training = ctx.meta
-        dc, dg, db = bn_bwd(dy.contiguous(), c, mean, invstd, g, b, training, ACT_GELU)
+        x, cw, g, b, c, mean, invstd, mod = ctx.saved_tensors
+        lvl, training, site = ctx.meta
+        dmod = _dmod(mod, site)
+        dc, dg, db = bn_bwd(dy.contiguous(), c, mean, invstd, g, b, training, ACT_GELU, mod, dmod, lvl)
         # policy (no input gradient): this is the LAST weight gradient of the backward pass and the critical stream has
         # nothing after the BatchNorm backward above — run it here instead of queueing it behind the side stream's tail
         dcw, _ = conv_wgrad(dc, x, cw.shape, lvl.nbr125, need_bias=False, side=ctx.needs_input_grad[0] or not _STEM_WGRAD_MAIN)
         # the policy feeds raw point features (no gradient); the motion planner concatenates a learned label embedding
         dx = conv_dgrad(dc, cw, lvl.nbr125, lvl.order[0], lvl=lvl) if ctx.needs_input_grad[0] else None
-        return dx, dcw, dg, db, None, None, None, None
+        return dx, dcw, dg, db, None, None, None, None, dmod, None, None
 
 
 class PoolFn(torch.autograd.Function):
     """SerializedPooling: GELU(BN(segment_max(Linear(x))))   (model.py:760-790)."""
 
     @_fwd
-    def forward(ctx, x, w, bias, g, b, rmean, rvar, child, training):
+    def forward(ctx, x, w, bias, g, b, rmean, rvar, child, training, mod=None, bank=None, j=0):
+        """(an adaptive norm sees the pooled level's clouds)"""
         (wk,), _ = _wk(w)
         ctx.wk = wk
         proj, _ = linear_fwd(x, wk, bias)
@@ -1752,57 +1840,62 @@ class PoolFn(torch.autograd.Function):
         call("lotus_pool_max_fwd", proj, child.members, child.seg_start, child.n, C, pooled, arg)
         if ARG_TAP is not None or ARG_INJECT:
             arg = _arg_hook("pool", arg)
-        y, mean, invstd = bn_fwd(pooled, g, b, rmean, rvar, training, ACT_GELU)
-        ctx.save_for_backward(x, w, g, b, pooled, arg, mean, invstd)
-        ctx.meta = (child, training)
+        y, mean, invstd = bn_fwd(pooled, g, b, rmean, rvar, training, ACT_GELU, mod=mod, lvl=child)
+        ctx.save_for_backward(x, w, g, b, pooled, arg, mean, invstd, mod)
+        ctx.meta = (child, training, (bank, j))
         return y
 
     @_joined
     def backward(ctx, dy):
-        x, w, g, b, pooled, arg, mean, invstd = ctx.saved_tensors
-        child, training = ctx.meta
+        x, w, g, b, pooled, arg, mean, invstd, mod = ctx.saved_tensors
+        child, training, site = ctx.meta
         C = w.shape[0]
-        dpool, dg, db = bn_bwd(dy.contiguous(), pooled, mean, invstd, g, b, training, ACT_GELU)
+        dmod = _dmod(mod, site)
+        dpool, dg, db = bn_bwd(dy.contiguous(), pooled, mean, invstd, g, b, training, ACT_GELU, mod, dmod, child)
         dproj = torch.empty(x.shape[0], C, dtype=x.dtype, device=x.device)
         call("lotus_pool_max_bwd", dpool, arg, child.cluster, x.shape[0], C, dproj)
         dw, dbias = linear_wgrad(dproj, x)
         dx = linear_dgrad(dproj, ctx.wk)
-        return dx, dw, dbias, dg, db, None, None, None, None
+        return dx, dw, dbias, dg, db, None, None, None, None, dmod, None, None
 
 
 class UnpoolFn(torch.autograd.Function):
     """SerializedUnpooling: skip = GELU(BN(Linear_skip(parent))), up = GELU(BN(Linear(point)));
-    returns (skip + up[cluster], skip)   (model.py:817-828).  `skip` alone feeds the decoder CPE conv."""
+    returns (skip + up[cluster], skip)   (model.py:817-828).  `skip` alone feeds the decoder CPE conv.  Adaptive norms: `up` is
+    modulated (modu, slice ju) per cloud of the coarse level `child`, `skip` (mods, js) per cloud of the fine one, `lvl`."""
 
     @_fwd
-    def forward(ctx, xc, xp, wu, bu, gu, betau, rmu, rvu, ws_, bs, gs, betas, rms, rvs, child, training):
+    def forward(ctx, xc, xp, wu, bu, gu, betau, rmu, rvu, ws_, bs, gs, betas, rms, rvs, child, training, modu=None, mods=None,
+                bank=None, ju=0, js=0, lvl=None):
         (wuk, wsk), _ = _wk(wu, ws_)
         ctx.wk = (wuk, wsk)
         lu, _ = linear_fwd(xc, wuk, bu)
         ls, _ = linear_fwd(xp, wsk, bs)
-        (up, mu, iu), (skip, ms, is_) = bn_fwd_pair(lu, (gu, betau, rmu, rvu), ls, (gs, betas, rms, rvs), training, ACT_GELU)
+        (up, mu, iu), (skip, ms, is_) = bn_fwd_pair(lu, (gu, betau, rmu, rvu, modu, child), ls, (gs, betas, rms, rvs, mods, lvl),
+                                                    training, ACT_GELU)
         x = torch.empty_like(skip)
         call("lotus_unpool_fwd", skip, up, child.cluster, skip.shape[0], skip.shape[1], x)
-        ctx.save_for_backward(xc, xp, wu, gu, betau, ws_, gs, betas, lu, ls, mu, iu, ms, is_)
-        ctx.meta = (child, training)
+        ctx.save_for_backward(xc, xp, wu, gu, betau, ws_, gs, betas, lu, ls, mu, iu, ms, is_, modu, mods)
+        ctx.meta = (child, training, lvl, (bank, ju), (bank, js))
         return x, skip
 
     @_joined
     def backward(ctx, dx, dskip):
-        xc, xp, wu, gu, betau, ws_, gs, betas, lu, ls, mu, iu, ms, is_ = ctx.saved_tensors
-        child, training = ctx.meta
+        xc, xp, wu, gu, betau, ws_, gs, betas, lu, ls, mu, iu, ms, is_, modu, mods = ctx.saved_tensors
+        child, training, lvl, su, ss = ctx.meta
         C = wu.shape[0]
         dx = dx.contiguous()
         dup = torch.empty(child.n, C, dtype=dx.dtype, device=dx.device)
         call("lotus_unpool_bwd", dx, child.members, child.seg_start, child.n, C, dup)
         dsk = add(dx, dskip.contiguous()) if dskip is not None else dx
-        (dlu, dgu, dbetau), (dls, dgs, dbetas) = bn_bwd_pair((dup, lu, mu, iu, gu, betau), (dsk, ls, ms, is_, gs, betas),
-                                                            training, ACT_GELU)
+        dmu, dms = _dmod(modu, su), _dmod(mods, ss)
+        (dlu, dgu, dbetau), (dls, dgs, dbetas) = bn_bwd_pair((dup, lu, mu, iu, gu, betau, modu, dmu, child),
+                                                            (dsk, ls, ms, is_, gs, betas, mods, dms, lvl), training, ACT_GELU)
         dwu, dbu = linear_wgrad(dlu, xc)
         dxc = linear_dgrad(dlu, ctx.wk[0])
         dws, dbs = linear_wgrad(dls, xp)
         dxp = linear_dgrad(dls, ctx.wk[1])
-        return dxc, dxp, dwu, dbu, dgu, dbetau, None, None, dws, dbs, dgs, dbetas, None, None, None, None
+        return (dxc, dxp, dwu, dbu, dgu, dbetau, None, None, dws, dbs, dgs, dbetas) + (None,) * 4 + (dmu, dms, None, None, None, None)
 
 
 class LinearFn(torch.autograd.Function):

@@ -78,21 +78,32 @@ class Block(nn.Module):
         self.norm2 = nn.Sequential(nn.LayerNorm(c))
         self.mlp = nn.Sequential(_MLP(c, int(c * mlp_ratio)))
 
-    def run(self, x, xs, lvl, drop_p, seed, attn_p=0.0, wt=None, dpath=0.0):
+    def run(self, x, xs, lvl, drop_p, seed, attn_p=0.0, wt=None, dpath=0.0, mods=None, bank=None, pid=None):
         """-> (x, hand): `hand` lets the next sub-block's backward pre-mask the gradient this block's MLP needs
         (ops.Handoff; the blocks of a stage form a chain with a single consumer each).  `lvl` carries the patch tables of
-        this block's curve slot (Level.for_order); dpath = DropPath rate of the attention and MLP branches (training)."""
-        c0, c1, c2 = self.cpe[0], self.cpe[1], self.cpe[2]
-        x = ops.CpeFn.apply(x, xs, c0.weight, c0.bias, c1.weight, c1.bias, c2.weight, c2.bias, lvl, wt)
-        a, n1 = self.attn, self.norm1[0]
-        h_attn, h_mlp = ops.Handoff(), ops.Handoff()
-        x = ops.SelfAttnFn.apply(x, n1.weight, n1.bias, a.qkv.weight, a.qkv.bias, a.q_norm.weight, a.q_norm.bias,
-                                 a.k_norm.weight, a.k_norm.bias, a.proj.weight, a.proj.bias, lvl, self.num_heads,
-                                 drop_p, seed, attn_p, h_attn, dpath)
-        m, n2 = self.mlp[0], self.norm2[0]
-        x = ops.FfnFn.apply(x, n2.weight, n2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, drop_p,
-                            ops.mix_seed(seed, 2), h_mlp, h_attn, dpath)
-        return x, (h_mlp if dpath == 0.0 else None)
+        this block's curve slot (Level.for_order); dpath = DropPath rate of the attention and MLP branches (training).
+        The walker of Block, concat.PlainBlock and adanorm.AdaBlock: attn.q_norm / k_norm may be nn.Identity, and with `mods`
+        (the slices of the adanorm.ModBank `bank`, pid = id(PDNorm) -> slice index) the three norms are PDNorms.  Hand-overs exist
+        for plain LayerNorms with q/k norm only."""
+        def site(n):  # a norm module -> (weight, bias), the nodes' trailing (mod, bank, j)
+            if mods is None:
+                return (n.weight, n.bias), ()
+            j = pid[id(n)]
+            return (n.norm.weight, n.norm.bias), (mods[j], bank, j)
+        c0, c1, a, m = self.cpe[0], self.cpe[1], self.attn, self.mlp[0]
+        gb, ada = site(self.cpe[2])
+        x = ops.CpeFn.apply(x, xs, c0.weight, c0.bias, c1.weight, c1.bias, *gb, lvl, wt, *ada)
+        qk = isinstance(a.q_norm, nn.LayerNorm)
+        qkn = (a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias) if qk else (None,) * 4
+        handed = qk and mods is None
+        h_attn, h_mlp = (ops.Handoff(), ops.Handoff()) if handed else (None, None)
+        gb, ada = site(self.norm1[0])
+        x = ops.SelfAttnFn.apply(x, *gb, a.qkv.weight, a.qkv.bias, *qkn, a.proj.weight, a.proj.bias, lvl, self.num_heads,
+                                 drop_p, seed, attn_p, h_attn, dpath, *ada)
+        gb, ada = site(self.norm2[0])
+        x = ops.FfnFn.apply(x, *gb, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, drop_p, ops.mix_seed(seed, 2), h_mlp,
+                            h_attn, dpath, lvl, *ada)
+        return x, (h_mlp if handed and dpath == 0.0 else None)
 
 
 class CABlock(nn.Module):

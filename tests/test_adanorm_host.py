@@ -128,3 +128,24 @@ def test_mean_reduce_needs_one_token_per_cloud():
     m = SimplePolicyPTV3AdaNorm(lcfg.preset("adanorm_tiny"))
     with pytest.raises(ValueError, match="one instruction token"):
         m.prepare_ptv3_batch(synth.synth_batch(2, 64, seed=0))
+
+
+def test_one_set_of_norm_site_nodes():
+    """The CA, AdaNorm and Concat backbones reach their stem, pooling, unpooling and Block sub-blocks through the six nodes of
+    ops.py and one block walker: adanorm.py and concat.py define no autograd node besides the modulation product and the two stems
+    with a pre-norm convolution of their own, and ops.py (which holds both norm families) does not import adanorm.py."""
+    from robot_3dlotus_amd import adanorm, concat, ops, ptv3
+
+    def nodes(mod):
+        return {n for n, c in vars(mod).items()
+                if isinstance(c, type) and issubclass(c, torch.autograd.Function) and c.__module__ == mod.__name__}
+
+    assert nodes(adanorm) == {"ModAllFn", "StemGroupsFn"}
+    assert nodes(concat) == {"CtxStemFn"}
+    assert {"StemFn", "PoolFn", "UnpoolFn", "CpeFn", "SelfAttnFn", "FfnFn"} <= nodes(ops)
+    assert adanorm.AdaBlock.run is ptv3.Block.run and concat.PlainBlock.run is ptv3.Block.run
+    assert not hasattr(concat.PlainBlock, "run_plain")
+    for cls in (adanorm.PointTransformerV3AdaNorm, concat.PointTransformerV3Plain):
+        assert cls.forward is ptv3.PointTransformerV3CA.forward and cls._run_stage is ptv3.PointTransformerV3CA._run_stage
+    assert concat.PointTransformerV3Plain._pool is ptv3.PointTransformerV3CA._pool
+    assert not any(v is adanorm for v in vars(ops).values())

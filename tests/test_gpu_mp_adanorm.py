@@ -181,7 +181,7 @@ def test_published_heatmap_head_on_the_adanorm_backbone():
 
 # ------------------------------------------------------------------------------------ the stem in two column groups
 def test_two_group_stem_equals_the_single_stem():
-    """c_pc = 4: [pc | one-hot] is 8 columns wide, which the thin-input stem takes in one call (adanorm.AdaStemFn, as the policy
+    """c_pc = 4: [pc | one-hot] is 8 columns wide, which the thin-input stem takes in one call (ops.StemFn, as the policy
     calls it).  The two-group route — conv(W_pc, pc) then conv(W_lab, one-hot) added onto it, a weight gradient per group — must
     give the same output and the same two weight gradients within the per-kernel bar."""
     from robot_3dlotus_amd import adanorm, ops
@@ -192,17 +192,17 @@ def test_two_group_stem_equals_the_single_stem():
     m.ptv3_model.order_perms = [[2, 0, 1, 3], [1, 3, 0, 2]]
     batch = _dev(mu.case_batch("mp_ada_tiny_train"))
     seen = {}
-    orig = adanorm.AdaStemGroupsFn.apply
+    orig = adanorm.StemGroupsFn.apply
 
     def spy(xa, xb, mod, wa, wb, g, b, rmean, rvar, lvl, training, bank, j):
         seen.update(xa=xa, xb=xb, mod=mod.detach(), g=g.detach(), b=b.detach(), lvl=lvl)
         return orig(xa, xb, mod, wa, wb, g, b, rmean, rvar, lvl, training, bank, j)
 
-    adanorm.AdaStemGroupsFn.apply = spy
+    adanorm.StemGroupsFn.apply = spy
     try:
         m(batch, compute_loss=True, compute_final_action=False)
     finally:
-        adanorm.AdaStemGroupsFn.apply = orig
+        adanorm.StemGroupsFn.apply = orig
     assert seen["xa"].shape[1] == 4 and seen["xb"].shape[1] == 4
     lvl, mod, g, b = seen["lvl"], seen["mod"], seen["g"], seen["b"]
     C = g.shape[0]
@@ -221,10 +221,10 @@ def test_two_group_stem_equals_the_single_stem():
         wl = w.clone().requires_grad_(True)
         rm, rv = torch.zeros(C, device="cuda"), torch.ones(C, device="cuda")
         if groups:
-            y = adanorm.AdaStemGroupsFn.apply(seen["xa"], seen["xb"], mod, wl[..., :4].contiguous(), wl[..., 4:].contiguous(), g, b,
-                                              rm, rv, lvl, True, _Bank(), 0)
+            y = adanorm.StemGroupsFn.apply(seen["xa"], seen["xb"], mod, wl[..., :4].contiguous(), wl[..., 4:].contiguous(), g, b,
+                                           rm, rv, lvl, True, _Bank(), 0)
         else:
-            y = adanorm.AdaStemFn.apply(torch.cat([seen["xa"], seen["xb"]], 1).contiguous(), mod, wl, g, b, rm, rv, lvl, True, _Bank(), 0)
+            y = ops.StemFn.apply(torch.cat([seen["xa"], seen["xb"]], 1).contiguous(), wl, g, b, rm, rv, lvl, True, mod, _Bank(), 0)
         y.backward(dy)
         ops.sync_side_stream()
         torch.cuda.synchronize()
