@@ -215,10 +215,31 @@ int lotus_conv_dup_fold(const lotus_act_t* dy, const long long* code0, const int
 int lotus_conv_dup_mask(lotus_act_t* dx, const lotus_act_t* add, const int* rep, int n, int C, void* stream);
 size_t lotus_subm_conv_wgrad_workspace(int n, int T, int cin, int cout);
 /* precision (0 fp32 | 1 bf16 | 3 bf16x3): operand mode of the products, as lotus_linear_wgrad; accumulation, the split
- * partials and the bias gradient (summed from the fp32 rows) stay fp32. */
+ * partials and the bias gradient (summed from the fp32 rows) stay fp32.
+ * PRECONDITION: the centre tap names a row for every row (nbr[T/2][p] >= 0), as every table of lotus_fe_neighbours does:
+ * db is summed over the pairs of that tap, and lotus_conv_dup_mask reads the same column as the voxel representative. */
 int lotus_subm_conv_wgrad(const lotus_act_t* dy, const lotus_act_t* x, float* dw, float* db, const int* nbr, int n, int T,
                           int cin, int cout, int accumulate, int precision, void* workspace, size_t workspace_bytes,
                           void* stream);
+/* Diagnostic: the kernel the calling thread's last convolution launch (lotus_subm_conv, lotus_subm_conv_wgrad; also inside
+ * lotus_cpe_fwd / _bwd) was given to, recorded where the kernel is chosen and before the launch is attempted (so it is there
+ * after a launch that failed, too).  A call that launches nothing (an argument refusal, n == 0) leaves the record as it was.
+ * out[8] = {family, mode, tile rows, tile columns, operand precision, nz, tpz, aux}:
+ *   family  1 conv_kernel (generic gather-GEMM)        2 conv_smallcin_kernel (thin-input stem, active pairs)
+ *           3 conv_pairs_kernel (pair-compacted)       4 conv_os_kernel (output-stationary)
+ *           5 tap-grouped dense products + tap sum     6 conv_wgrad_kernel (fp32 products)
+ *           7 conv_wgrad_bf16_kernel                   8 conv_smallcin_wgrad_kernel (thin-input stem, needs db == NULL)
+ *   mode    0 fwd, 1 dgrad, 2 wgrad
+ *   rows    output rows per block tile: 128 (1, 4), 32 (2), 64 per row tile (3), 64-row tap segments (5); 64 output
+ *           channels per block (6, 7, 8)
+ *   columns output columns per block: 64 | 128 (1), 64 (2), 64 | 128 = 32 NCS (3), 64 | 128 = 32 NS (4), the output width
+ *           (5); input channels per block 64 (6, 7), 8 (8)
+ *   precision the operand mode of the kernel that runs: 0 exact fp32, 1 bf16, 3 bf16x3 (families 1, 2, 5, 6, 8: always 0)
+ *   nz      tap groups (3, 4: 1, 3 or 9, summed by conv_part_reduce_kernel when > 1; 5: 27; 1, 2: 1) or row splits (6-8)
+ *   tpz     taps per group (3, 4: ceil(27 / nz); 1, 2: T; 5: 1) or rows per split (6-8)
+ *   aux     2: the CIN template (4, 6, 7, 8, or 0 = run-time width); 4: KCH, the reduction chunk (64 | 128);
+ *           6-8: 1 when the single split writes dw / db directly (no reduction launch), 0 when partial slabs are reduced */
+int lotus_conv_last_route(int* out);
 
 /* ---- normalisation ------------------------------------------------------------------------ */
 /* nn.LayerNorm (model.py:624,627,645; model_ca.py:114,124): y = LN(x) (+ res) */

@@ -12,6 +12,7 @@
 // spatially coherent: taps with no active neighbour in the block are skipped for the whole block,
 // and per-wave 32-row groups skip their MFMAs through a ballot mask.
 #include "mma.h"
+#include "conv_route.h"
 
 namespace LOTUS_NS {
 
@@ -674,6 +675,7 @@ int lotus_subm_conv(int mode, const act_t* x, const float* w, const float* w_t, 
     LOTUS_CHECK_ARG((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y) | ((uintptr_t)bias) | ((uintptr_t)add)) % 16 == 0,
                     "lotus_subm_conv: the tap-grouped path needs 16-byte aligned operands");
     const int n64 = (n + 63) / 64 * 64, ND = mode == 0 ? cout : cin;
+    lotus_note_conv_route(LOTUS_CONV_TAP, mode, 64, ND, 0, 27, 1, 0);
     const int rc = lotus_conv_tap_gemm(mode, x, w, (float*)workspace, tap_plan + 32, tap_plan, n64, n, cin, cout, (hipStream_t)stream);
     if (rc != LOTUS_OK) return rc;
     const long total4 = (long)n * ND / 4;
@@ -705,6 +707,7 @@ int lotus_subm_conv(int mode, const act_t* x, const float* w, const float* w_t, 
                        cin);
     p.w = (const float*)workspace;
     const dim3 sg(cout / 64, cdiv(n, STEM_ROWS));
+    lotus_note_conv_route(LOTUS_CONV_STEM, 0, STEM_ROWS, 64, 0, 1, T, (cin == 4 || (cin >= 6 && cin <= 8)) ? cin : 0);
     if (cin == 7) LOTUS_LAUNCH((conv_smallcin_kernel<7>), sg, dim3(256), 0, st, p);
     else if (cin == 8) LOTUS_LAUNCH((conv_smallcin_kernel<8>), sg, dim3(256), 0, st, p);
     else if (cin == 6) LOTUS_LAUNCH((conv_smallcin_kernel<6>), sg, dim3(256), 0, st, p);
@@ -716,6 +719,7 @@ int lotus_subm_conv(int mode, const act_t* x, const float* w, const float* w_t, 
   dim3 block(256);
   const size_t dyn = conv_dyn_lds(T, 128);
   LOTUS_CHECK_ARG(dyn + 20000 <= 160 * 1024, "lotus_subm_conv: %d taps do not fit LDS", T);
+  lotus_note_conv_route(LOTUS_CONV_GENERIC, mode, 128, p.ND <= 64 ? 64 : 128, 0, 1, T, 0);
   if (p.ND <= 64) {
     dim3 grid(cdiv(p.ND, 64), cdiv(n, 128));
     if (mode == 0) {
@@ -895,6 +899,9 @@ size_t lotus_subm_conv_wgrad_workspace(int n, int T, int cin, int cout) {
 }
 
 // dw [cout][T][cin] (+)= sum_p dy[p] (x) x[nbr[t][p]] ;  db [cout] (+)= colsum(dy)
+// PRECONDITION: the centre tap (t = T / 2) names a row for EVERY row, nbr[T / 2][p] >= 0 — as every table of
+// lotus_fe_neighbours does (a point is in its own voxel).  db is summed by the centre-tap blocks over the pairs of that tap,
+// and lotus_conv_dup_mask reads the same column as the voxel representative; a table with a hole there loses that row's dy.
 int lotus_subm_conv_wgrad(const act_t* dy, const act_t* x, float* dw, float* db, const int* nbr, int n, int T,
                           int cin, int cout, int accumulate, int precision, void* workspace, size_t workspace_bytes,
                           void* stream) {
@@ -916,7 +923,10 @@ int lotus_subm_conv_wgrad(const act_t* dy, const act_t* x, float* dw, float* db,
     p.part = (float*)workspace; p.part_stride = (long)slab;
     p.bias_part = db ? p.part + wsz : nullptr;
   }
-  if (cin <= 8 && cout % 64 == 0 && !db) {  // thin-input stem: VALU kernel over the active pairs
+  const bool stem = cin <= 8 && cout % 64 == 0 && !db;
+  lotus_note_conv_route(stem ? LOTUS_CONV_WGRAD_STEM : precision ? LOTUS_CONV_WGRAD_BF16 : LOTUS_CONV_WGRAD, 2, 64, stem ? 8 : 64,
+                        stem ? 0 : precision, nsplit, p.chunk, direct ? 1 : 0);
+  if (stem) {  // thin-input stem: VALU kernel over the active pairs
     LOTUS_LAUNCH(conv_smallcin_wgrad_kernel, dim3(cout / 64, T, nsplit), dim3(256), 0, st, p);
   } else {
     dim3 grid(cdiv(cout, 64) * cdiv(cin, 64), T, nsplit);
@@ -930,6 +940,13 @@ int lotus_subm_conv_wgrad(const act_t* dy, const act_t* x, float* dw, float* db,
   int rc = lotus_reduce_parts(p.part, dw, (long)wsz, (long)slab, nsplit, accumulate, st);
   if (!rc && db) rc = lotus_reduce_parts(p.part + wsz, db, cout, (long)slab, nsplit, accumulate, st);
   return rc;
+}
+
+// diagnostic: the kernel the calling thread's last convolution launch was given to (conv_route.h; fields in lotus_hip.h)
+int lotus_conv_last_route(int* out) {
+  LOTUS_CHECK_ARG(out, "lotus_conv_last_route: out is null");
+  for (int i = 0; i < 8; ++i) out[i] = lotus_tls_conv_route[i];
+  return LOTUS_OK;
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 // into MFMA B fragments (k is permuted identically on both operands: lane-half h takes
 // k = h*KC/2 + s, so every lane reads a contiguous run).
 #include "mma.h"
+#include "conv_route.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -831,6 +832,7 @@ static int launch_pairs_p(ConvP2& p, int nz, hipStream_t st) {
   static bool attr_set = false;  // per instantiation; the attribute call costs host time on every launch otherwise
   if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_pairs_kernel<NCS, PREC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); attr_set = true; }
   dim3 grid(p.ND / (32 * NCS), cdiv(p.n, Cfg::BM * Cfg::NRT), nz);
+  lotus_note_conv_route(LOTUS_CONV_PAIRS, p.mirror, Cfg::BM, 32 * NCS, PREC, nz, p.tpz, 0);
   LOTUS_LAUNCH((conv_pairs_kernel<NCS, PREC>), grid, dim3(256), sm, st, p);
   LOTUS_LAUNCH_CHECK("lotus_subm_conv(pairs)");
   return LOTUS_OK;
@@ -864,6 +866,7 @@ static int launch_os_t(ConvP2& p, int nz, hipStream_t st) {
   static bool attr_set = false;
   if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_os_kernel<PREC, NS, KCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); attr_set = true; }
   dim3 grid(p.ND / Cfg::NW, cdiv(p.n, Cfg::BR), nz);
+  lotus_note_conv_route(LOTUS_CONV_OS, p.mirror, Cfg::BR, Cfg::NW, PREC, nz, p.tpz, KCH);
   LOTUS_LAUNCH((conv_os_kernel<PREC, NS, KCH>), grid, dim3(256), sm, st, p);
   LOTUS_LAUNCH_CHECK("lotus_subm_conv(output-stationary bf16)");
   return LOTUS_OK;

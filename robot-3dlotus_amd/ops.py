@@ -42,6 +42,20 @@ def last_dense_route():
     return DenseRoute(*out)
 
 
+ConvRoute = collections.namedtuple("ConvRoute", "family mode rows cols prec nz tpz aux")
+(CONV_GENERIC, CONV_STEM, CONV_PAIRS, CONV_OS, CONV_TAP, CONV_WGRAD, CONV_WGRAD_BF16, CONV_WGRAD_STEM) = range(1, 9)
+
+
+def last_conv_route():
+    """The kernel this thread's last convolution launch was given to (lotus_conv_last_route; fields in include/lotus_hip.h):
+    family 1 generic, 2 thin-input stem, 3 pair-compacted, 4 output-stationary, 5 tap-grouped, 6 / 7 / 8 weight gradient
+    (fp32, bf16 operands, thin-input stem); mode 0 fwd / 1 dgrad / 2 wgrad; block tile; operand precision; tap groups (or row
+    splits) and taps (rows) per group; aux.  Set when the kernel is chosen, so it is there after a launch that failed, too."""
+    out = (ctypes.c_int * 8)()
+    _capi.call_raw("lotus_conv_last_route", ctypes.addressof(out))
+    return ConvRoute(*out)
+
+
 class _Timed:
     """Bracket a dense launch with HIP events on the stream it is enqueued on (diagnostic; only when EVENT_LOG is set)."""
 

@@ -436,12 +436,17 @@ def test_subm_conv_edges(scene, cin, cout):
     wt = ops.conv_weight_t(wc)
     rec, fails = {"rows": n}, []
     for path, plan in (("tap_plan", L.tap_plan), ("pairs", None)):
+        family = ops.CONV_TAP if plan is not None else ops.CONV_PAIRS
         y = ops.conv_fwd(xc, wc, bc, L.nbr27, L.order[0], add=addc, w_t=wt, tap_plan=plan)
+        r = ops.last_conv_route()
+        assert (r.family, r.mode, r.nz) == (family, 0, 27 if plan is not None else 9), (path, r)
         fails.append(_bar(rec, f"fwd_{path}", y, yref + add.double(), 3e-6))
         if scene == "isolated":  # only the centre tap: a second, independent reference
             centre = x.double() @ w.double().reshape(cout, 27, cin)[:, 13, :].T + b.double() + add.double()
             fails.append(_bar(rec, f"fwd_{path}_vs_centre_tap", y, centre, 3e-6))
         d = ops.conv_dgrad(dyc, wc, L.nbr27, L.order[0], add=adddc, w_t=wt, lvl=lvl, tap_plan=plan)
+        r = ops.last_conv_route()
+        assert (r.family, r.mode, r.nz) == (family, 1, 27 if plan is not None else 9), (path, r)
         fails.append(_bar(rec, f"dgrad_{path}", d, xd.grad + addd.double(), 3e-6))
         if scene == "dups":
             naive = ops.conv_dgrad(dyc, wc, L.nbr27, L.order[0], add=adddc, w_t=wt, tap_plan=plan)  # mirrored taps only
@@ -450,6 +455,8 @@ def test_subm_conv_edges(scene, cin, cout):
         d2 = ops.conv_dgrad(dyc, wc, L.nbr27, L.order[0], add=adddc, w_t=wt, lvl=lvl, tap_plan=plan)
         assert torch.equal(y, y2) and torch.equal(d, d2), f"{path}: two runs must be bit-equal"
     dw, db = ops.conv_wgrad(dyc, xc, w.shape, L.nbr27)
+    r = ops.last_conv_route()
+    assert (r.family, r.mode, r.nz, r.aux) == (ops.CONV_WGRAD, 2, (n + 1023) // 1024, 1 if n <= 1024 else 0), r
     dw, db = dw.clone(), db.clone()
     fails.append(_bar(rec, "wgrad", dw, wd.grad, 5e-6))
     fails.append(_bar(rec, "bgrad", db, bd.grad, 5e-6))

@@ -182,6 +182,20 @@ def _cloud_levels(B, n, seed, n_levels=2):
     return batch, ref, got
 
 
+def _packed_family(ops, kd, prec=0):
+    """The kernel family a 3^3 convolution with packed weights is given to in THIS process (the switches are read once per
+    process; test_subm_conv_bf16_operands_pair_compacted_path re-runs these tests under each of them)."""
+    import os
+    if kd % 64 == 0 and ((prec and os.environ.get("LOTUS_CONV_OS", "1") != "0") or (not prec and os.environ.get("LOTUS_CONV_OS_F32") == "1")):
+        return ops.CONV_OS
+    return ops.CONV_PAIRS
+
+
+def _took(ops, family, mode, what, **fields):
+    r = ops.last_conv_route()
+    assert (r.family, r.mode) == (family, mode) and all(getattr(r, k) == v for k, v in fields.items()), (what, r)
+
+
 @pytest.mark.parametrize("cin,cout,k", [(64, 64, 3), (128, 128, 3), (7, 64, 5), (256, 128, 3)])
 def test_subm_conv_fwd_dgrad_wgrad(cin, cout, k):
     ops = _ops()
@@ -197,25 +211,32 @@ def test_subm_conv_fwd_dgrad_wgrad(cin, cout, k):
     xd, wd, bd = x.double().requires_grad_(True), w.double().requires_grad_(True), b.double().requires_grad_(True)
     yref = om.subm_conv(xd, nbr_ref, wd, bd)
     y = ops.conv_fwd(x.cuda(), w.cuda(), b.cuda(), nbr, got[0].order[0])
+    _took(ops, ops.CONV_GENERIC if k == 3 else ops.CONV_STEM, 0, "conv fwd without packed weights", **({} if k == 3 else dict(aux=7)))
     _close(y, yref, 3e-6, "conv fwd")
     wt = ops.conv_weight_t(w.cuda()) if k == 3 else None
     if k == 3:
         y2 = ops.conv_fwd(x.cuda(), w.cuda(), b.cuda(), nbr, got[0].order[0], w_t=wt)
+        _took(ops, _packed_family(ops, cin), 0, "conv fwd (packed weights)", cols=min(cout, 128), nz=9)
         _close(y2, yref, 3e-6, "conv fwd (pair-compacted, packed weights)")
     yref.backward(dy.double())
     if cin == cout:
         dx = ops.conv_dgrad(dy.cuda(), w.cuda(), nbr, got[0].order[0])
+        _took(ops, ops.CONV_GENERIC, 1, "conv dgrad without packed weights")
         _close(dx, xd.grad, 3e-6, "conv dgrad")
     dw, db = ops.conv_wgrad(dy.cuda(), x.cuda(), w.shape, nbr)
+    _took(ops, ops.CONV_WGRAD, 2, "conv wgrad", nz=(n + 1023) // 1024, aux=int(n <= 1024))
     _close(dw, wd.grad, 5e-6, "conv wgrad")
     _close(db, bd.grad, 5e-6, "conv bgrad")
     dw2, _ = ops.conv_wgrad(dy.cuda(), x.cuda(), w.shape, nbr, need_bias=False)  # (thin inputs: active-pair VALU kernel)
+    _took(ops, ops.CONV_WGRAD_STEM if cin == 7 else ops.CONV_WGRAD, 2, "conv wgrad (no bias)")
     _close(dw2, wd.grad, 5e-6, "conv wgrad (no bias)")
     if cin != cout and k == 3:
         dx = ops.conv_dgrad(dy.cuda(), w.cuda(), nbr, None)
+        _took(ops, ops.CONV_GENERIC, 1, "conv dgrad (natural row order)", cols=128 if cin > 64 else 64)
         _close(dx, xd.grad, 3e-6, "conv dgrad (cin != cout, natural row order)")
     if k == 3:
         dx = ops.conv_dgrad(dy.cuda(), w.cuda(), nbr, got[0].order[0], w_t=wt)
+        _took(ops, _packed_family(ops, cout), 1, "conv dgrad (packed weights)", cols=min(cin, 128), nz=9)
         _close(dx, xd.grad, 3e-6, "conv dgrad (pair-compacted, packed weights)")
 
 
@@ -253,11 +274,15 @@ def test_subm_conv_level0_of_64_clouds(path):
     xc, dyc, wc = x.cuda(), dy.cuda(), w.cuda()
     wt = ops.conv_weight_t(wc)
     plan = L.tap_plan if path == "tap_plan" else None
+    want = dict(family=ops.CONV_TAP, nz=27, tpz=1) if path == "tap_plan" else dict(family=ops.CONV_PAIRS, cols=64, nz=1, tpz=27)
     y = ops.conv_fwd(xc, wc, b.cuda(), L.nbr27, L.order[0], add=add.cuda(), w_t=wt, tap_plan=plan)
+    _took(ops, want.pop("family"), 0, f"conv fwd ({path})", **want)
     _close(y, yr, 3e-6, "conv fwd")
     d = ops.conv_dgrad(dyc, wc, L.nbr27, L.order[0], add=add.cuda(), w_t=wt, lvl=L, tap_plan=plan)
+    _took(ops, ops.CONV_TAP if path == "tap_plan" else ops.CONV_PAIRS, 1, f"conv dgrad ({path})", **want)
     _close(d, dr, 3e-6, "conv dgrad")
     dw, db = ops.conv_wgrad(dyc, xc, w.shape, L.nbr27)
+    _took(ops, ops.CONV_WGRAD, 2, "conv wgrad", nz=256, tpz=1024, aux=0)
     _close(dw, dwr.reshape(w.shape), 5e-6, "conv wgrad")
     _close(db, dy.double().sum(0), 5e-6, "conv bgrad")
     y2 = ops.conv_fwd(xc, wc, b.cuda(), L.nbr27, L.order[0], add=add.cuda(), w_t=wt, tap_plan=plan)
@@ -356,8 +381,11 @@ def test_subm_conv_bf16_operand_paths(prec, cin, cout):
     try:
         wt = ops.conv_weight_t(w.cuda())
         y = ops.conv_fwd(x.cuda(), w.cuda(), None, got[0].nbr27, got[0].order[0], w_t=wt)
+        _took(ops, _packed_family(ops, cin, prec), 0, "conv fwd", prec=prec, cols=min(cout, 128))
         dx = ops.conv_dgrad(dy.cuda(), w.cuda(), got[0].nbr27, got[0].order[0], w_t=wt)
+        _took(ops, _packed_family(ops, cout, prec), 1, "conv dgrad", prec=prec, cols=min(cin, 128))
         dw, db = ops.conv_wgrad(dy.cuda(), x.cuda(), w.shape, got[0].nbr27)
+        _took(ops, ops.CONV_WGRAD_BF16, 2, "conv wgrad", prec=prec)
     finally:
         ops.set_gemm_precision("fp32")
     rnd = (lambda t: t.bfloat16().double()) if prec == 1 else (lambda t: t.double())
