@@ -25,6 +25,7 @@
  *       LOTUS_CONV_TAP_MINC=c         tap-grouped dense path from c channels (default 64)
  *       LOTUS_CONV_TAP_SLAB_MB=m      ... while its partial slab stays below m MB (default 2047)
  *       LOTUS_CONV_WG_CHUNK=n         points per split of the sparse-convolution weight gradient (default 1024)
+ *       LOTUS_CONV_WG_TILE=128|128x64|64x128  cout x cin tile of its fp32 kernel (diagnostic; default 64 x 64; read per call)
  *       LOTUS_CONV_OS=0               bf16 operand modes use the pair-compacted convolution kernel
  *       LOTUS_CONV_OS_F32=1|2|3       exact-fp32 products on the output-stationary convolution kernel (opt-in)
  *       LOTUS_XQ=0|2|3                cross attention on the tile kernels / patch attention on the per-query kernels / the
@@ -231,9 +232,9 @@ int lotus_subm_conv_wgrad(const lotus_act_t* dy, const lotus_act_t* x, float* dw
  *           7 conv_wgrad_bf16_kernel                   8 conv_smallcin_wgrad_kernel (thin-input stem, needs db == NULL)
  *   mode    0 fwd, 1 dgrad, 2 wgrad
  *   rows    output rows per block tile: 128 (1, 4), 32 (2), 64 per row tile (3), 64-row tap segments (5); 64 output
- *           channels per block (6, 7, 8)
+ *           channels per block (6, 7, 8; 6: 128 where LOTUS_CONV_WG_TILE asks for it)
  *   columns output columns per block: 64 | 128 (1), 64 (2), 64 | 128 = 32 NCS (3), 64 | 128 = 32 NS (4), the output width
- *           (5); input channels per block 64 (6, 7), 8 (8)
+ *           (5); input channels per block 64 (6, 7; 6: 128 where LOTUS_CONV_WG_TILE asks for it), 8 (8)
  *   precision the operand mode of the kernel that runs: 0 exact fp32, 1 bf16, 3 bf16x3 (families 1, 2, 5, 6, 8: always 0)
  *   nz      tap groups (3, 4: 1, 3 or 9, summed by conv_part_reduce_kernel when > 1; 5: 27; 1, 2: 1) or row splits (6-8)
  *   tpz     taps per group (3, 4: ceil(27 / nz); 1, 2: T; 5: 1) or rows per split (6-8)

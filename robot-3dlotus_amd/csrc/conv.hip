@@ -11,6 +11,8 @@
 // Output rows are processed in serialised (space-filling-curve) order so that a 128-row block is
 // spatially coherent: taps with no active neighbour in the block are skipped for the whole block,
 // and per-wave 32-row groups skip their MFMAs through a ballot mask.
+#include <type_traits>
+
 #include "mma.h"
 #include "conv_route.h"
 
@@ -255,19 +257,47 @@ struct ConvWgP {
 };
 #define WG_MAX_PAIRS 2048
 
+#define WG_NO_PAIR 0xffffu  // pair_p of a padding pair (a split has at most WG_MAX_PAIRS rows)
+
+// One gathered operand row segment, base[r][c .. c + 3], AS LOADED: the load is issued for every pair — a padding pair
+// (r = -1) reads the last row and is zeroed (zsel4) when its slab is staged — because a load under a branch makes the
+// compiler drain every outstanding load at the join, the slabs in flight with it.  `colp` = base + c is the lane's column
+// pointer, computed once; FAST (block-uniform) = the whole tile lies inside the matrix and 16-byte loads are legal, so
+// the row id is all that is left to add.
+template <bool FAST>
+__device__ __forceinline__ float4 wg_row4(const act_t* __restrict__ base, const act_t* __restrict__ colp, int ld, int r, int c,
+                                          int rmax, int cmax, bool vec_ok) {
+  const int rc = (int)min((unsigned)r, (unsigned)(rmax - 1));
+  if (FAST) return ld4(colp + (long)rc * ld);
+  return load4_guard(base, ld, rc, c, rmax, cmax, vec_ok);
+}
+__device__ __forceinline__ float4 zsel4(bool ok, float4 v) {
+  return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
+}
+
+// Tile BM (cout) x BN (cin) of dW[:, t, :] over the pairs of one split: 4 waves 2 x 2, (BM / 64) x (BN / 64) accumulators
+// of 32 x 32 per wave.  Slabs of LOTUS_BK pairs run through a two-stage LDS image (one barrier per slab) with the gathers
+// of the next two slabs in flight in registers.  Every output element sums its pairs in compacted order, k-step by k-step
+// as mma_slab maps them, whatever the tile: dw and db do not depend on it, bit for bit.
+// The step runs 64 x 64 (wg_tile): a 128-wide side halves the gathered bytes per product, but a block then lives 2 - 4
+// times as long, the centre-tap blocks (every row of the split is a pair) become the kernel's tail, and fewer blocks fit a
+// CU; measured slower at every level of the bench batch, alone and in the step (profiles/r07_conv_wgrad.md).
+template <int BM, int BN>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvWgP p) {
-  constexpr int BM = 64, BN = 64;
-  __shared__ float As[LOTUS_BK * BM];
-  __shared__ float Bs[LOTUS_BK * BN];
-  __shared__ int pair_p[WG_MAX_PAIRS + LOTUS_BK];
-  __shared__ int pair_q[WG_MAX_PAIRS + LOTUS_BK];
+  constexpr int TM = BM / 64, TN = BN / 64;
+  __shared__ __attribute__((aligned(16))) float As[2][LOTUS_BK * BM];
+  __shared__ __attribute__((aligned(16))) float Bs[2][LOTUS_BK * BN];
+  constexpr int PAD = 3 * LOTUS_BK;  // the last slab's padding pairs and the two slabs gathered beyond it
+  __shared__ unsigned short pair_p[WG_MAX_PAIRS + PAD];  // dy row - p0
+  __shared__ int pair_q[WG_MAX_PAIRS + PAD];             // x row
+  static_assert(sizeof(As) + sizeof(Bs) + sizeof(pair_p) + sizeof(pair_q) <= 46 * 1024, "LDS budget of a block");
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int tiles_ci = (p.cin + BN - 1) / BN;
-  const int co0 = (blockIdx.x / tiles_ci) * BM, ci0 = (blockIdx.x % tiles_ci) * BN;
-  const int t = blockIdx.y;
-  const int p0 = blockIdx.z * p.chunk, p1 = min(p.n, p0 + p.chunk);
-  const int wr0 = (wave >> 1) * 32, wc0 = (wave & 1) * 32;
+  const int bx = blockIdx.x, bz = blockIdx.z, t = blockIdx.y;
+  const int co0 = (bx / tiles_ci) * BM, ci0 = (bx % tiles_ci) * BN;
+  const int p0 = bz * p.chunk, p1 = min(p.n, p0 + p.chunk);
+  const int wr0 = (wave >> 1) * (BM / 2), wc0 = (wave & 1) * (BN / 2);
 
   // ordered compaction of the active (p, q = nbr[t][p]) pairs of this split: the neighbour ids of all its 256-row
   // windows are loaded up front (one memory latency for the split instead of one per window plus three barriers each)
@@ -298,67 +328,122 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvWgP p) {
       }
       if (qv[w] >= 0) {
         const int rank = __popcll(bv[w] & ((1ull << lane) - 1ull));
-        pair_p[off + rank] = p0 + w * 256 + tid;
+        pair_p[off + rank] = (unsigned short)(w * 256 + tid);
         pair_q[off + rank] = qv[w];
       }
     }
   }
   __syncthreads();
-  const int total_s = total_r;
-  const int total = total_s;
-  for (int i = total + tid; i < total + LOTUS_BK; i += 256) {
-    pair_p[i] = -1;
+  const int total = total_r;
+  for (int i = total + tid; i < total + PAD; i += 256) {
+    pair_p[i] = WG_NO_PAIR;
     pair_q[i] = -1;
   }
   __syncthreads();
 
-  f32x16 acc[1][1];
+  f32x16 acc[TM][TN];
+  float asum[TM];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
-  float asum[1] = {0.f};
+  for (int i = 0; i < TM; ++i) {
+    asum[i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  }
   const bool a_vec = (p.cout % 4 == 0) && (((uintptr_t)p.dy) % 16 == 0);
   const bool b_vec = (p.cin % 4 == 0) && (((uintptr_t)p.x) % 16 == 0);
-  const int kr = tid / 16, cq = tid % 16;  // one float4 per thread per operand: row kr, cols cq*4..
+  // a slab is LOTUS_BK rows of BM (BN) floats: TM (TN) float4 per thread and operand, rows kra + q * RA, columns cqa * 4 ..
+  constexpr int RA = 1024 / BM, RB = 1024 / BN;
+  const int kra = tid / (BM / 4), cqa = tid % (BM / 4), krb = tid / (BN / 4), cqb = tid % (BN / 4);
+  const int ca = co0 + cqa * 4, cb = ci0 + cqb * 4;
+  const act_t* const pa = p.dy + ca;
+  const act_t* const pb = p.x + cb;
+  const int nslab = (total + LOTUS_BK - 1) / LOTUS_BK;
 
-  float4 ra, rb;
-  auto gload = [&](int k0) {
-    const int pp = pair_p[k0 + kr], qq = pair_q[k0 + kr];
-    ra = pp >= 0 ? load4_guard(p.dy, p.cout, pp, co0 + cq * 4, p.n, p.cout, a_vec) : make_float4(0.f, 0.f, 0.f, 0.f);
-    rb = qq >= 0 ? load4_guard(p.x, p.cin, qq, ci0 + cq * 4, p.n, p.cin, b_vec) : make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto lstore = [&]() {
-    st4(&As[kr * BM + cq * 4], ra);
-    st4(&Bs[kr * BN + cq * 4], rb);
-  };
-  if (total > 0) {
-    gload(0);
-    lstore();
+  auto run = [&](auto fast) __attribute__((always_inline)) {
+    constexpr bool FAST = decltype(fast)::value;
+    struct Regs { float4 a[TM], b[TN]; bool oka[TM], okb[TN]; };
+    auto gload = [&](Regs& g, int s) __attribute__((always_inline)) {
+      int pp[TM], qq[TN];  // (all row ids before the first load that depends on one)
+#pragma unroll
+      for (int q = 0; q < TM; ++q) {
+        const unsigned o = pair_p[s * LOTUS_BK + kra + q * RA];
+        pp[q] = o == WG_NO_PAIR ? -1 : p0 + (int)o;
+      }
+#pragma unroll
+      for (int q = 0; q < TN; ++q) qq[q] = pair_q[s * LOTUS_BK + krb + q * RB];
+#pragma unroll
+      for (int q = 0; q < TM; ++q) {
+        g.oka[q] = (unsigned)pp[q] < (unsigned)p.n;
+        g.a[q] = wg_row4<FAST>(p.dy, pa, p.cout, pp[q], ca, p.n, p.cout, a_vec);
+      }
+#pragma unroll
+      for (int q = 0; q < TN; ++q) {
+        g.okb[q] = (unsigned)qq[q] < (unsigned)p.n;
+        g.b[q] = wg_row4<FAST>(p.x, pb, p.cin, qq[q], cb, p.n, p.cin, b_vec);
+      }
+    };
+    auto lstore = [&](int buf, const Regs& g) __attribute__((always_inline)) {
+#pragma unroll
+      for (int q = 0; q < TM; ++q) st4(&As[buf][(kra + q * RA) * BM + cqa * 4], zsel4(g.oka[q], g.a[q]));
+#pragma unroll
+      for (int q = 0; q < TN; ++q) st4(&Bs[buf][(krb + q * RB) * BN + cqb * 4], zsel4(g.okb[q], g.b[q]));
+    };
+    // slab s is multiplied out of LDS stage s & 1 while slab s + 1 waits in one register set and slab s + 2 is being
+    // gathered into the other; the stage written behind the products is the one the previous slab was read from, which
+    // every wave left at the previous barrier.  Two slabs per trip keep the register sets static, and the gathers run
+    // unconditionally up to two slabs past the end (padding pairs, staged as zeros and never multiplied) so that the
+    // wait in front of a stage counts the loads issued after its own instead of draining them.
+    Regs g0, g1;
+    gload(g0, 0);
+    gload(g1, 1);
+    lstore(0, g0);
     __syncthreads();
-    for (int k0 = 0; k0 < total; k0 += LOTUS_BK) {
-      const bool more = k0 + LOTUS_BK < total;
-      if (more) gload(k0 + LOTUS_BK);
-      mma_slab<BM, BN, false, false, true>(As, Bs, wr0, wc0, acc, asum);
+    int s = 0;
+    // (the scheduling fences keep the gathers in front of the products and the staging behind them: left alone the
+    // compiler sinks the loads below the MFMAs and waits for them at the top of the next slab)
+    for (; s + 1 < nslab; s += 2) {
+      gload(g0, s + 2);
+      __builtin_amdgcn_sched_barrier(0);
+      mma_slab<BM, BN, false, false, true>(As[0], Bs[0], wr0, wc0, acc, asum);
+      __builtin_amdgcn_sched_barrier(0);
+      lstore(1, g1);
       __syncthreads();
-      if (more) {
-        lstore();
-        __syncthreads();
+      gload(g1, s + 3);
+      __builtin_amdgcn_sched_barrier(0);
+      mma_slab<BM, BN, false, false, true>(As[1], Bs[1], wr0, wc0, acc, asum);
+      __builtin_amdgcn_sched_barrier(0);
+      lstore(0, g0);
+      __syncthreads();
+    }
+    if (s < nslab) mma_slab<BM, BN, false, false, true>(As[0], Bs[0], wr0, wc0, acc, asum);
+  };
+  if (nslab > 0) {
+    if (a_vec && b_vec && co0 + BM <= p.cout && ci0 + BN <= p.cin) run(std::true_type{});
+    else run(std::false_type{});
+  }
+  float* part = p.part + (long)bz * p.part_stride;
+#pragma unroll
+  for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {
+      const int col = ci0 + acc_col(wc0, tn);
+      if (col >= p.cin) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = co0 + acc_row(wr0, tm, r);
+        if (row < p.cout) part[((long)row * p.T + t) * p.cin + col] = acc[tm][tn][r];
       }
     }
-  }
-  float* part = p.part + (long)blockIdx.z * p.part_stride;
-  const int col = ci0 + acc_col(wc0, 0);
-  if (col < p.cin) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = co0 + acc_row(wr0, 0, r);
-      if (row < p.cout) part[((long)row * p.T + t) * p.cin + col] = acc[0][0][r];
-    }
-  }
   // bias gradient = column sums of dy over all points: the centre tap is active for every point
   if (p.bias_part && t == p.T / 2 && ci0 == 0 && (wave & 1) == 0) {
-    const float s = asum[0] + __shfl_xor(asum[0], 32, 64);
-    const int i = co0 + wr0 + (tid & 31);
-    if ((tid & 32) == 0 && i < p.cout) p.bias_part[(long)blockIdx.z * p.part_stride + i] = s;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {
+      const float s = asum[tm] + __shfl_xor(asum[tm], 32, 64);
+      const int i = co0 + wr0 + tm * 32 + (tid & 31);
+      if ((tid & 32) == 0 && i < p.cout) p.bias_part[(long)bz * p.part_stride + i] = s;
+    }
   }
 }
 
@@ -366,9 +451,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvWgP p) {
 // dense layers, gemm.hip): same decomposition and pair compaction, 32 pairs per slab; the gathered dy / x rows are
 // converted (and split) while they are staged into k-contiguous bf16 images (mma.h BTile, pair index = k), the products
 // are v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  The bias gradient is summed from the fp32 staging registers.
-__device__ __forceinline__ float4 zsel4(bool ok, float4 v) {
-  return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
-}
 
 template <int PREC>
 __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(ConvWgP p) {
@@ -893,6 +975,19 @@ static int wg_chunk() {
   return c;
 }
 
+// Tile of conv_wgrad_kernel: 64 x 64.  LOTUS_CONV_WG_TILE=128 | 128x64 | 64x128 (diagnostic; read at every call, so that one
+// process can compare the forms) asks for 128 on the sides named — cout x cin — and gets it on a side whose width is >= 128
+// and a multiple of 64; the route record names the tile that runs.
+static void wg_tile(int cin, int cout, int* bm, int* bn) {
+  *bm = *bn = 64;
+  const char* e = getenv("LOTUS_CONV_WG_TILE");
+  if (!e) return;
+  const char* x = strchr(e, 'x');
+  const bool wide_m = atoi(e) == 128, wide_n = atoi(x ? x + 1 : e) == 128;
+  if (wide_m && cout >= 128 && cout % 64 == 0) *bm = 128;
+  if (wide_n && cin >= 128 && cin % 64 == 0) *bn = 128;
+}
+
 size_t lotus_subm_conv_wgrad_workspace(int n, int T, int cin, int cout) {
   const int nsplit = cdiv(n > 0 ? n : 1, wg_chunk());
   return (size_t)nsplit * ((size_t)cout * T * cin + cout) * sizeof(float);
@@ -924,15 +1019,20 @@ int lotus_subm_conv_wgrad(const act_t* dy, const act_t* x, float* dw, float* db,
     p.bias_part = db ? p.part + wsz : nullptr;
   }
   const bool stem = cin <= 8 && cout % 64 == 0 && !db;
-  lotus_note_conv_route(stem ? LOTUS_CONV_WGRAD_STEM : precision ? LOTUS_CONV_WGRAD_BF16 : LOTUS_CONV_WGRAD, 2, 64, stem ? 8 : 64,
+  int bm = 64, bn = 64;
+  if (!stem && !precision) wg_tile(cin, cout, &bm, &bn);
+  lotus_note_conv_route(stem ? LOTUS_CONV_WGRAD_STEM : precision ? LOTUS_CONV_WGRAD_BF16 : LOTUS_CONV_WGRAD, 2, bm, stem ? 8 : bn,
                         stem ? 0 : precision, nsplit, p.chunk, direct ? 1 : 0);
   if (stem) {  // thin-input stem: VALU kernel over the active pairs
     LOTUS_LAUNCH(conv_smallcin_wgrad_kernel, dim3(cout / 64, T, nsplit), dim3(256), 0, st, p);
   } else {
-    dim3 grid(cdiv(cout, 64) * cdiv(cin, 64), T, nsplit);
+    dim3 grid(cdiv(cout, bm) * cdiv(cin, bn), T, nsplit);
     if (precision == 1) LOTUS_LAUNCH(conv_wgrad_bf16_kernel<1>, grid, dim3(256), 0, st, p);
     else if (precision == 3) LOTUS_LAUNCH(conv_wgrad_bf16_kernel<3>, grid, dim3(256), 0, st, p);
-    else LOTUS_LAUNCH(conv_wgrad_kernel, grid, dim3(256), 0, st, p);
+    else if (bm == 128 && bn == 128) LOTUS_LAUNCH((conv_wgrad_kernel<128, 128>), grid, dim3(256), 0, st, p);
+    else if (bm == 128) LOTUS_LAUNCH((conv_wgrad_kernel<128, 64>), grid, dim3(256), 0, st, p);
+    else if (bn == 128) LOTUS_LAUNCH((conv_wgrad_kernel<64, 128>), grid, dim3(256), 0, st, p);
+    else LOTUS_LAUNCH((conv_wgrad_kernel<64, 64>), grid, dim3(256), 0, st, p);
   }
   LOTUS_LAUNCH_CHECK("lotus_subm_conv_wgrad");
   if (direct) return LOTUS_OK;

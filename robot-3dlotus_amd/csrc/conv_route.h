@@ -10,7 +10,7 @@
 #define LOTUS_CONV_PAIRS 3        // conv_pairs_kernel<NCS, PREC> (+ conv_part_reduce_kernel when nz > 1)
 #define LOTUS_CONV_OS 4           // conv_os_kernel<PREC, NS, KCH> (+ conv_part_reduce_kernel when nz > 1)
 #define LOTUS_CONV_TAP 5          // gemm_dma_tap_kernel / gemm_kernel over the tap plan + conv_tap_reduce_kernel
-#define LOTUS_CONV_WGRAD 6        // conv_wgrad_kernel
+#define LOTUS_CONV_WGRAD 6        // conv_wgrad_kernel<64 | 128, 64 | 128>
 #define LOTUS_CONV_WGRAD_BF16 7   // conv_wgrad_bf16_kernel<PREC>
 #define LOTUS_CONV_WGRAD_STEM 8   // conv_smallcin_wgrad_kernel
 
