@@ -11,16 +11,16 @@ SelfAttnFn / FfnFn, per launch — handed the site's modulation slice: the norm 
 bn_bwd and their pair forms) then call the modulated-norm entry points of csrc/adanorm.hip.  Under data parallel
 (parallel.GradReducer + parallel.enable_sync_batchnorm) the 13 BatchNorm sites of a five-stage model run split — statistics ->
 one fp64 message per site and direction (the two unpooling branches share theirs: 9 forward + 9 backward) -> apply.  All modulation projections
-of a forward pass are one product (ModAllFn; the same idea as ops.KvAllFn for the CABlocks): SiLU(c) [B, 256] against the
-concatenated weights of every PDNorm, and one weight-gradient / one input-gradient product in backward over the d mod slab
-that the norms' backward passes fill in place.  fp32 activation storage only.
+of a forward pass are one product (ops.ProjAllFn with pre = "silu", the node that projects the keys / values of the CABlocks):
+SiLU(c) [B, 256] against the concatenated weights of every PDNorm, and one weight-gradient / one input-gradient product in
+backward over the gradient slab of the ops.ProjBank that the norms' backward passes fill in place.  fp32 activation storage only.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import ops
-from .ops import ACT_GELU, _fwd, _joined, silu
+from .ops import ACT_GELU, _fwd, _joined
 from .ptv3 import Block, PointTransformerV3CA, SubMConv3d, _Attn, _MLP, _bn
 
 
@@ -57,64 +57,6 @@ def _adabn_bwd_stats(dy, x, mean, invstd, g, b, mod, dmod, lvl, act, sums):
 
 def _adabn_bwd_apply_sums(dy, x, mean, invstd, g, b, mod, lvl, act, sums):
     return ops._bn_bwd_apply(dy, x, mean, invstd, g, b, True, act, sums, (None, None), mod, None, lvl)[0]
-
-
-# ------------------------------------------------------------------------------------ modulation bank
-class ModBank:
-    """[shift | scale] of every PDNorm of one forward pass: `mod` [B, sum 2C_j], norm j in columns offs[j] : offs[j] + 2C_j.
-    `dmod` (same shape) collects d mod, each norm's backward writing its own column slice."""
-    __slots__ = ("mod", "dmod", "offs", "widths", "slices")
-
-    def slice(self, j):
-        return self.slices[j]
-
-    def grad_slice(self, j):
-        if self.dmod is None:
-            self.dmod = torch.empty_like(self.mod)
-        return self.dmod[:, self.offs[j]:self.offs[j] + self.widths[j]]
-
-
-class ModAllFn(torch.autograd.Function):
-    """mod_j = Linear_j(SiLU(c)) for every PDNorm j in ONE product: SiLU(c) [B, Cc] x cat(W_j) [sum 2C_j, Cc] (v1: 40 norms,
-    24 064 columns).  The weights stay the modules' own parameters; their concatenation is one copy per step."""
-
-    @_fwd
-    def forward(ctx, context, bank, *wb):
-        ws, bs = wb[0::2], wb[1::2]
-        W = torch.cat(ws, 0)
-        bias = torch.cat(bs, 0)
-        s = silu(context)
-        mod, _ = ops.linear_fwd(s, W, bias)
-        bank.mod, bank.dmod = mod, None
-        bank.widths = [w.shape[0] for w in ws]
-        bank.offs = [0]
-        for w_ in bank.widths[:-1]:
-            bank.offs.append(bank.offs[-1] + w_)
-        bank.slices = tuple(mod[:, o:o + w_] for o, w_ in zip(bank.offs, bank.widths))
-        ctx.bank = bank
-        ctx.save_for_backward(context, s, W)
-        return bank.slices
-
-    @_joined
-    def backward(ctx, *gs):
-        context, s, W = ctx.saved_tensors
-        bank = ctx.bank
-        if bank.dmod is None:
-            bank.dmod = torch.empty_like(bank.mod)
-        dmod = bank.dmod
-        for j, g in enumerate(gs):  # normally every g IS its slice of the slab (written in place by the norm's backward)
-            sl = dmod[:, bank.offs[j]:bank.offs[j] + bank.widths[j]]
-            if g is None:
-                sl.zero_()
-            elif g.data_ptr() != sl.data_ptr() or g.stride() != sl.stride():
-                sl.copy_(g)
-        dW, db = ops.linear_wgrad(dmod, s)
-        dctx = silu(context, ops.linear_dgrad(dmod, W)) if ctx.needs_input_grad[0] else None
-        out = [dctx, None]
-        for o, w_ in zip(bank.offs, bank.widths):
-            out += [dW[o:o + w_], db[o:o + w_]]
-        bank.dmod = None
-        return tuple(out)
 
 
 # ------------------------------------------------------------------------------------ the two-group stem
@@ -297,8 +239,8 @@ class PointTransformerV3AdaNorm(PointTransformerV3CA):
 
     def _begin(self, fw, data_dict, feat):
         """Top of a pass -> stem output: the modulation bank of every PDNorm, the stem, then the join of the packed weights."""
-        fw.bank = ModBank()
-        fw.mods = ModAllFn.apply(fw.context, fw.bank, *self._mod_params())
+        fw.bank = ops.ProjBank()
+        fw.mods = ops.ProjAllFn.apply(fw.context, fw.bank, "silu", *self._mod_params())
         st = self.embedding.stem
         nb, j = st.norm.norm, self._pd_index[id(st.norm)]
         groups = data_dict.get("stem_groups")

@@ -56,9 +56,27 @@ class TrajectoryActionHead(nn.Module):
                                         nn.Dropout(dropout), nn.Linear(hidden_size, self.euler_bins * 3 + 1 + 1))
 
 
+class _Prefetched:
+    """What prefetch() built ahead of forward(): entries (pc_fts, pc_labels, built), matched by the identity of the batch's two
+    tensors.  At most two are kept (the batch about to run and the one after it); a consumed entry is forgotten."""
+
+    def __init__(self):
+        self.entries = []
+
+    def remember(self, batch, built):
+        self.entries = (self.entries + [(batch["pc_fts"], batch["pc_labels"], built)])[-2:]
+
+    def take(self, batch):
+        """-> what remember() was given for this very batch, or None."""
+        hit = next((q for q in self.entries if q[0] is batch["pc_fts"] and q[1] is batch["pc_labels"]), None)
+        self.entries = [q for q in self.entries if q is not hit][-1:]  # (at most one more: the batch after this one)
+        return None if hit is None else hit[2]
+
+
 class MotionPlannerPTV3CA(BaseModel):
     def __init__(self, config):
         super().__init__()
+        self._pre = _Prefetched()
         config = to_cfg(config)
         self.config = config
         act = config.action_config
@@ -86,7 +104,6 @@ class MotionPlannerPTV3CA(BaseModel):
 
     def prepare_ptv3_batch(self, batch):
         """motion_planner_ptv3.py:433-463: feat = [pc_fts | label embedding], context = txt_fc(txt_embeds)."""
-        labels = batch["pc_labels"].long()
         # The 64 embedding channels take only 4 distinct values per point, and the stem convolution is linear:
         #   conv(W, [pc | E[label]]) == conv([W_pc | W_emb E^T], [pc | onehot(label)])
         # so the 68-channel 5^3 convolution (81 % of whose gathered rows are absent neighbours) becomes the 8-channel
@@ -95,13 +112,8 @@ class MotionPlannerPTV3CA(BaseModel):
         W, E = self.ptv3_model.embedding.stem.conv.weight, self.pc_label_embedding.weight
         c_pc = batch["pc_fts"].shape[1]
         w_eff = torch.cat([W[..., :c_pc], torch.matmul(W[..., c_pc:], E.t())], -1)                  # [64,5,5,5,c_pc+4]
-        pres = getattr(self, "_pre", None) or []
-        pre = next((q for q in pres if q[0] is batch["pc_fts"] and q[1] is batch["pc_labels"]), None)
-        self._pre = [q for q in pres if q is not pre][-1:]  # (at most one more: the batch after this one)
-        if pre is not None:
-            feat = pre[2]   # prefetch() built it (and started the front-end on exactly this tensor)
-        else:
-            feat = torch.cat([batch["pc_fts"].float(), F.one_hot(labels, 4).float()], -1)
+        feat = self._pre.take(batch)   # prefetch() built it (and started the front-end on exactly this tensor)
+        feat = self._point_input(batch) if feat is None else feat
         txt, extra = batch["txt_embeds"].contiguous(), {}
         if getattr(self, "act_storage", None) == "bf16":
             # bf16 activation storage (as SimplePolicyPTV3CA.prepare_ptv3_batch): the network inputs are rounded once here;
@@ -118,13 +130,18 @@ class MotionPlannerPTV3CA(BaseModel):
                 "feat": feat_in, "stem_weight": w_eff.contiguous(), "context": ctx, "counts": list(batch["npoints_in_batch"]),
                 "context_counts": ctx_counts, **extra}
 
+    @staticmethod
+    def _point_input(batch):
+        """-> [pc | one-hot label] [N, c_pc + 4] fp32."""
+        return torch.cat([batch["pc_fts"].float(), F.one_hot(batch["pc_labels"].long(), 4).float()], -1)
+
     @torch.no_grad()
     def prefetch(self, batch):
         """Input-pipeline hook, as SimplePolicyPTV3CA.prefetch: build the network input of `batch` ([pc | one-hot label]) and
         start its integer front-end on the side stream; the following forward(batch) must get the same (device) batch."""
         batch = self.prepare_batch(batch)
-        feat = torch.cat([batch["pc_fts"].float(), F.one_hot(batch["pc_labels"].long(), 4).float()], -1)
-        self._pre = ((getattr(self, "_pre", None) or []) + [(batch["pc_fts"], batch["pc_labels"], feat)])[-2:]
+        feat = self._point_input(batch)
+        self._pre.remember(batch, feat)
         self.ptv3_model.prefetch({"coord": feat[:, :3], "grid_size": self.config.action_config.voxel_size, "offset": batch["offset"],
                                   "feat": feat, "counts": list(batch["npoints_in_batch"]),
                                   "context_counts": [c + int(bool(self.config.action_config.use_ee_pose)) for c in batch["txt_lens"]]})
@@ -140,13 +157,16 @@ class MotionPlannerPTV3CA(BaseModel):
             return self._forward(batch, compute_loss, **kwargs)
 
     def _forward(self, batch, compute_loss=False, **kwargs):
+        """The planner's one forward; what differs between the heat-map head and the soft head ('heatmap_mlp',
+        MotionPlannerPTV3AdaNorm) are its three steps _positions, _pos_loss_term and _final_positions."""
         batch = self.prepare_batch(batch)
         dev = self.hip_device(batch)
-        act, head = self.config.action_config, self.act_proj_head
-        last = self.ptv3_model(self.prepare_ptv3_batch(batch), return_dec_layers=True)[-1]
+        head = self.act_proj_head
+        d = self.prepare_ptv3_batch(batch)
+        last = self.ptv3_model(d, return_dec_layers=True)[-1]
         x, lvl = last.feat, last.level
         B, T, C = len(lvl.counts), head.max_traj_len, head.hidden_size
-        nb, eb = 2 * head.pos_bins, head.euler_bins
+        eb = head.euler_bins
         p = head.dropout if self.training else 0.0
         hm, am = head.heatmap_mlp, head.action_mlp
         te = head.traj_embedding.weight                                         # [T, E]
@@ -155,8 +175,7 @@ class MotionPlannerPTV3CA(BaseModel):
         # point-feature product is shared by all T steps and the step only shifts the bias.
         base = ops.LinearFn.apply(x, hm[0].weight[:, :C].contiguous(), None)                       # [N, C]
         step_bias = F.linear(te, hm[0].weight[:, C:], hm[0].bias)                                  # [T, C]
-        xts = list(ops.StepHeadFn.apply(base, step_bias.contiguous(), hm[3].weight, hm[3].bias, p,
-                                        ops.mix_seed(self.ptv3_model.last_seed, 2000)))         # T x [N, 3*nb]
+        pos = self._positions(base, step_bias.contiguous(), hm[3], d, lvl, p, ops.mix_seed(self.ptv3_model.last_seed, 2000))
         # action branch, :116-120,139-146: max over points commutes with the concatenated step embedding
         pc = ops.CloudMaxFn.apply(x, lvl)                                                         # [B, C]
         pcs = torch.cat([pc.unsqueeze(1).expand(-1, T, -1), te.to(pc.dtype).unsqueeze(0).expand(B, -1, -1)], -1).reshape(B * T, -1)
@@ -164,25 +183,31 @@ class MotionPlannerPTV3CA(BaseModel):
         ae = ops.LinearFn.apply(a, am[3].weight, am[3].bias).view(B, T, -1)
         pred_rot = ae[..., :eb * 3].reshape(B, T, eb, 3)
         pred_open, pred_stop = ae[..., -2], ae[..., -1]
-        self.last_pred = (xts, pred_rot, pred_open, pred_stop)   # xts[t] is [N, 3*nb]; reference layout: pred_pos()
+        self.last_pred = (pos, pred_rot, pred_open, pred_stop)
 
-        losses = None
-        if compute_loss:
-            losses = self._traj_losses(xts, ae, batch, lvl)
+        losses = self._traj_losses(pos, ae, batch, lvl) if compute_loss else None
         decode = kwargs.get("compute_final_action", True)
         if compute_loss and self.training and not decode and not kwargs.get("decode_actions", False):
             return None, losses                                  # trainer discards the actions (see policy.py)
-        if decode:   # :238-267, best_disc_pos == 'max'; one launch pair per step instead of B*T host round trips
-            pcf = batch["pc_fts"] if batch["pc_fts"].stride(1) == 1 else batch["pc_fts"].contiguous()
-            best = act.get("best_disc_pos", "max")
-            pos = torch.stack([self.decode_disc_pos(best, xt.detach(), pcf, batch["npoints_in_batch"], lvl, nb, act.pos_bin_size)
-                               for xt in xts], 1)
-            pos = pos.float()                                    # reference: .float() at :266
-        else:
-            pos = batch["gt_trajs"][..., :3].float()
+        final_pos = self._final_positions(pos, batch, lvl, decode)
         quat = self.decode_euler_disc(pred_rot.reshape(B * T, eb, 3), head.euler_resolution, dev).reshape(B, T, 4)
-        final = torch.cat([pos, quat, pred_open.detach().unsqueeze(-1), pred_stop.detach().unsqueeze(-1)], -1)
+        final = torch.cat([final_pos, quat, pred_open.detach().unsqueeze(-1), pred_stop.detach().unsqueeze(-1)], -1)
         return (final, losses) if compute_loss else final
+
+    def _positions(self, base, step_bias, out, d, lvl, p, seed):
+        """-> last_pred[0]: the T heat maps xts[t] [N, 3*nb] (reference layout: pred_pos()); out = heatmap_mlp.3, d = the backbone's input."""
+        return list(ops.StepHeadFn.apply(base, step_bias, out.weight, out.bias, p, seed))
+
+    def _final_positions(self, xts, batch, lvl, decode):
+        """:238-267, best_disc_pos == 'max'; one launch pair per step instead of B*T host round trips."""
+        if not decode:
+            return batch["gt_trajs"][..., :3].float()
+        act, nb = self.config.action_config, 2 * self.act_proj_head.pos_bins
+        pcf = batch["pc_fts"] if batch["pc_fts"].stride(1) == 1 else batch["pc_fts"].contiguous()
+        best = act.get("best_disc_pos", "max")
+        pos = torch.stack([self.decode_disc_pos(best, xt.detach(), pcf, batch["npoints_in_batch"], lvl, nb, act.pos_bin_size)
+                           for xt in xts], 1)
+        return pos.float()                                       # reference: .float() at :266
 
     def pred_pos(self):
         """Last forward's position logits in the reference layout (T, 3, N, 2*pos_bins)."""
@@ -195,12 +220,24 @@ class MotionPlannerPTV3CA(BaseModel):
         ae = torch.cat([pred_rot.reshape(B, T, -1), pred_open.unsqueeze(-1), pred_stop.unsqueeze(-1)], -1)
         return self._traj_losses(xts, ae, batch, lvl)
 
-    def _traj_losses(self, xts, ae, batch, lvl):
-        """ae [B, T, euler_bins * 3 + 2]: rotation logits (bin, axis) at bin * 3 + axis | openness | stop."""
-        dev = ae.device
+    def _traj_losses(self, pos, ae, batch, lvl):
+        """pos = last_pred[0]; ae [B, T, euler_bins * 3 + 2]: rotation logits (bin, axis) at bin * 3 + axis | openness | stop."""
         B, T = ae.shape[:2]
         gt = batch["gt_trajs"].float()
         m = batch["traj_masks"].float()                                                  # [B, T]
+        node, term = self._pos_loss_term(pos, batch, lvl, T)
+        # the position term's masked mean (:327-336), masked rotation CE, openness and stop BCE (:338-383): one launch for the
+        # lot (the same arithmetic as ~40 small ATen kernels cost 2 ms per step)
+        lc = self.config.loss_config
+        L = node.apply(ae.reshape(B * T, -1), term.reshape(B * T, 3), gt.reshape(B * T, -1).contiguous(),
+                       batch["gt_trajs_stop"].float().reshape(-1).contiguous(), m.reshape(B, T).contiguous(),
+                       (ae.shape[-1] - 2) // 3, lc.pos_weight, lc.rot_weight)
+        return {"pos": L[0], "rot": L[1], "open": L[2], "stop": L[3], "total": L[4]}
+
+    def _pos_loss_term(self, xts, batch, lvl, T):
+        """-> (the loss node, its position input [B, T, 3]): ops.TrajLossFn over the heat-map cross entropies per (cloud, step,
+        axis) — sum_tc CE * mask / (3 * sum_t mask) per cloud, mean over clouds."""
+        dev = xts[0].device
         dp = batch["gt_trajs_disc_pos_probs"]
         # per step t the targets in the layout the CE kernel reads: cloud-major, [3][n_b * nb] per cloud
         if isinstance(dp, torch.Tensor):
@@ -208,14 +245,7 @@ class MotionPlannerPTV3CA(BaseModel):
         else:
             tgts = torch.cat([d.to(dev).float().reshape(T, -1) for d in dp], 1)
         tgts = tgts.contiguous()
-        ce = torch.stack([ops.PosCEFn.apply(xts[t], tgts[t], lvl) for t in range(T)], 1)  # [B, T, 3]
-        # sum_tc CE * mask / (3 * sum_t mask) per cloud, mean over clouds (:327-336); masked rotation CE, openness and
-        # stop BCE (:338-383): one launch for the lot (the same arithmetic as ~40 small ATen kernels cost 2 ms per step)
-        lc = self.config.loss_config
-        L = ops.TrajLossFn.apply(ae.reshape(B * T, -1), ce.reshape(B * T, 3), gt.reshape(B * T, -1).contiguous(),
-                                 batch["gt_trajs_stop"].float().reshape(-1).contiguous(), m.reshape(B, T).contiguous(),
-                                 (ae.shape[-1] - 2) // 3, lc.pos_weight, lc.rot_weight)
-        return {"pos": L[0], "rot": L[1], "open": L[2], "stop": L[3], "total": L[4]}
+        return ops.TrajLossFn, torch.stack([ops.PosCEFn.apply(xts[t], tgts[t], lvl) for t in range(T)], 1)
 
 
 class MotionPlannerPTV3AdaNorm(MotionPlannerPTV3CA):
@@ -236,13 +266,9 @@ class MotionPlannerPTV3AdaNorm(MotionPlannerPTV3CA):
             raise NotImplementedError(f"txt_reduce={act.txt_reduce!r}: MotionPlannerPTV3AdaNorm builds 'mean' and 'attn'")
         return PointTransformerV3AdaNorm(**p3)
 
-    def _point_input(self, batch):
-        """-> (pc [N, c_pc] fp32 contiguous, one-hot label [N, 4]); prefetch() may have built them already."""
-        pres = getattr(self, "_pre", None) or []
-        pre = next((q for q in pres if q[0] is batch["pc_fts"] and q[1] is batch["pc_labels"]), None)
-        self._pre = [q for q in pres if q is not pre][-1:]  # (at most one more: the batch after this one)
-        if pre is not None:
-            return pre[2], pre[3]
+    @staticmethod
+    def _point_input(batch):
+        """-> (pc [N, c_pc] fp32 contiguous, one-hot label [N, 4]): the two column groups, never concatenated."""
         return batch["pc_fts"].float().contiguous(), F.one_hot(batch["pc_labels"].long(), 4).float()
 
     def prepare_ptv3_batch(self, batch):
@@ -254,7 +280,7 @@ class MotionPlannerPTV3AdaNorm(MotionPlannerPTV3CA):
         from .adanorm import cloud_context
 
         act = self.config.action_config
-        pc, onehot = self._point_input(batch)
+        pc, onehot = self._pre.take(batch) or self._point_input(batch)   # (prefetch() may have built them already)
         c_pc = pc.shape[1]
         if c_pc > 8:
             raise NotImplementedError(f"MotionPlannerPTV3AdaNorm: pc_fts with {c_pc} > 8 columns (the thin-input stem convolution "
@@ -282,8 +308,8 @@ class MotionPlannerPTV3AdaNorm(MotionPlannerPTV3CA):
         """Input-pipeline hook, as MotionPlannerPTV3CA.prefetch: build the network input of `batch` and start its integer
         front-end on the side stream; the following forward(batch) must get the same (device) batch."""
         batch = self.prepare_batch(batch)
-        pc, onehot = batch["pc_fts"].float().contiguous(), F.one_hot(batch["pc_labels"].long(), 4).float()
-        self._pre = ((getattr(self, "_pre", None) or []) + [(batch["pc_fts"], batch["pc_labels"], pc, onehot)])[-2:]
+        pc, onehot = self._point_input(batch)
+        self._pre.remember(batch, (pc, onehot))
         self.ptv3_model.prefetch({"coord": pc[:, :3], "grid_size": self.config.action_config.voxel_size, "offset": batch["offset"],
                                   "feat": pc, "counts": list(batch["npoints_in_batch"]),
                                   "context_counts": [1] * len(batch["npoints_in_batch"])})
@@ -298,55 +324,26 @@ class MotionPlannerPTV3AdaNorm(MotionPlannerPTV3CA):
                                           f"only, got {mode!r}")
         return super().forward(batch, compute_loss, **kwargs)
 
-    def _forward(self, batch, compute_loss=False, **kwargs):
-        if self.act_proj_head.pos_pred_type != "heatmap_mlp":
-            return super()._forward(batch, compute_loss, **kwargs)
-        batch = self.prepare_batch(batch)
-        dev = self.hip_device(batch)
-        act, head = self.config.action_config, self.act_proj_head
-        d = self.prepare_ptv3_batch(batch)
-        last = self.ptv3_model(d, return_dec_layers=True)[-1]
-        x, lvl = last.feat, last.level
-        B, T, C = len(lvl.counts), head.max_traj_len, head.hidden_size
-        eb = head.euler_bins
-        p = head.dropout if self.training else 0.0
-        hm, am = head.heatmap_mlp, head.action_mlp
-        te = head.traj_embedding.weight                                         # [T, E]
+    @property
+    def _soft(self):
+        return self.act_proj_head.pos_pred_type == "heatmap_mlp"
 
-        # heatmap branch, motion_planner_ptv3.py:89-109: Linear([x | te_t]) = x Wx^T + (te_t Wt^T + b); the T hidden layers,
-        # the 4-column product, the per-cloud softmax and the weighted coordinates are one pass over `base`
-        base = ops.LinearFn.apply(x, hm[0].weight[:, :C].contiguous(), None)                       # [N, C]
-        step_bias = F.linear(te, hm[0].weight[:, C:], hm[0].bias)                                  # [T, C]
-        xt = ops.TrajSoftPosFn.apply(base, step_bias.contiguous(), hm[3].weight, hm[3].bias, d["feat"], lvl,
-                                     float(act.get("pos_heatmap_temp", 1)), p,
-                                     ops.mix_seed(self.ptv3_model.last_seed, 2000))                # [B, T, 3]
-        # action branch, :116-120,139-146, as MotionPlannerPTV3CA
-        pc = ops.CloudMaxFn.apply(x, lvl)                                                         # [B, C]
-        pcs = torch.cat([pc.unsqueeze(1).expand(-1, T, -1), te.to(pc.dtype).unsqueeze(0).expand(B, -1, -1)], -1).reshape(B * T, -1)
-        a = F.dropout(F.leaky_relu(ops.LinearFn.apply(pcs, am[0].weight, am[0].bias), 0.02), p, self.training)
-        ae = ops.LinearFn.apply(a, am[3].weight, am[3].bias).view(B, T, -1)
-        pred_rot = ae[..., :eb * 3].reshape(B, T, eb, 3)
-        pred_open, pred_stop = ae[..., -2], ae[..., -1]
-        self.last_pred = (xt, pred_rot, pred_open, pred_stop)
+    def _positions(self, base, step_bias, out, d, lvl, p, seed):
+        """'heatmap_mlp', motion_planner_ptv3.py:89-109 -> xt [B, T, 3]: the T hidden layers, the 4-column product, the per-cloud
+        softmax and the weighted coordinates are one pass over `base`."""
+        if not self._soft:
+            return super()._positions(base, step_bias, out, d, lvl, p, seed)
+        temp = float(self.config.action_config.get("pos_heatmap_temp", 1))
+        return ops.TrajSoftPosFn.apply(base, step_bias, out.weight, out.bias, d["feat"], lvl, temp, p, seed)
 
-        losses = None
-        if compute_loss:
-            lc = self.config.loss_config
-            L = ops.TrajRegLossFn.apply(ae.reshape(B * T, -1), xt.reshape(B * T, 3),
-                                        batch["gt_trajs"].float().reshape(B * T, -1).contiguous(),
-                                        batch["gt_trajs_stop"].float().reshape(-1).contiguous(),
-                                        batch["traj_masks"].float().reshape(B, T).contiguous(), eb, lc.pos_weight, lc.rot_weight)
-            losses = {"pos": L[0], "rot": L[1], "open": L[2], "stop": L[3], "total": L[4]}
-        decode = kwargs.get("compute_final_action", True)
-        if compute_loss and self.training and not decode and not kwargs.get("decode_actions", False):
-            return None, losses                                  # trainer discards the actions (see policy.py)
-        # :243,276-294: the continuous position is final as it is; float64 quaternions promote the whole action
-        quat = self.decode_euler_disc(pred_rot.reshape(B * T, eb, 3), head.euler_resolution, dev).reshape(B, T, 4)
-        final = torch.cat([xt.detach(), quat, pred_open.detach().unsqueeze(-1), pred_stop.detach().unsqueeze(-1)], -1)
-        return (final, losses) if compute_loss else final
+    def _pos_loss_term(self, xt, batch, lvl, T):
+        """'heatmap_mlp': ops.TrajRegLossFn, the masked MSE of xt with one global normalisation (:338-397)."""
+        return (ops.TrajRegLossFn, xt) if self._soft else super()._pos_loss_term(xt, batch, lvl, T)
+
+    def _final_positions(self, xt, batch, lvl, decode):
+        """:243,276-294: the continuous position is final as it is (the float64 quaternions promote the whole action)."""
+        return xt.detach() if self._soft else super()._final_positions(xt, batch, lvl, decode)
 
     def pred_pos(self):
         """Last forward's position: xt [B, T, 3] ('heatmap_mlp'), or the logits in the reference layout ('heatmap_disc')."""
-        if self.act_proj_head.pos_pred_type == "heatmap_mlp":
-            return self.last_pred[0]
-        return super().pred_pos()
+        return self.last_pred[0] if self._soft else super().pred_pos()

@@ -7,10 +7,13 @@ backward that chains the HIP kernels (fused epilogues, no temporaries beyond wha
   SelfAttnFn   x + proj(patch_attention(qkv(LN(x))))               Block.attn   model.py:664-667,468-557
   FfnFn        x + fc2(GELU(fc1(LN(x))))                           Block.mlp / CABlock.mlp
   CrossAttnFn  x + proj(cross_attention(q(LN(x)), kv(context)))    CABlock.attn model_ca.py:135-140
-  StemFn / PoolFn / UnpoolFn / HeadLossFn                          Embedding, SerializedPooling,
-                                                                   SerializedUnpooling, ActionHead+loss
-  RegHeadLossFn                                                    ActionHead+loss with heatmap_mlp positions and / or
-                                                                   euler / quat rotations (csrc/reg_head.hip)
+  CrossAttnKvFn  ... with kv a slice of the ProjBank               (the default: kv_group)
+  ProjAllFn    Linear_j(context) / Linear_j(SiLU(context)), all j  the kv of every CABlock / the modulation of every PDNorm
+  StemFn / PoolFn / UnpoolFn                                       Embedding, SerializedPooling, SerializedUnpooling
+  HeadLossFn / RegHeadLossFn                                       ActionHead+loss: published / with heatmap_mlp positions
+                                                                   and / or euler / quat rotations (csrc/reg_head.hip)
+The per-launch bodies are functions shared by the nodes that run them: cpe_ / selfattn_ / ffn_ / crossattn_branch_fwd / _bwd,
+head_trunk_fwd / _bwd, cloud_max_fwd.
 PyTorch provides device memory, the stream and the autograd graph; all arithmetic is in the kernels.
 """
 import collections
@@ -1289,6 +1292,53 @@ def ffn_branch_bwd(dy, n, hpre, a, w1, w2, p, seed, dpath, hand):
     return dn, dw1, db1, dw2, db2
 
 
+def crossattn_branch_fwd(n, x, wq, bq, kv, qn, kn, wp, bp, lvl, H, drop_p, seed, attn_p, own=None):
+    """n = LN(x), kv = [k | v] [L, 2C] (row stride free: a ProjBank slice) -> (y, q, att, lse, kv), y = x + drop(proj(CrossAttention(
+    q(n), kv))).  own = (context, wkv, bkv) instead of kv: the block's own projection (CrossAttnFn), launched behind q's."""
+    N, C = x.shape
+    q, _ = linear_fwd(n, wq, bq)
+    if own is not None:
+        kv, _ = linear_fwd(*own)
+    att = torch.empty(N, C, dtype=x.dtype, device=x.device)
+    lse = torch.empty(N, H, dtype=torch.float32, device=x.device)
+    attention_fwd(q, C, 0, kv, kv.stride(0), 0, C, None, None, None, lvl.ca_tiles, lvl.n_ca_tiles, qn, kn, att, lse, H, C // H,
+                  attn_p, mix_seed(seed, 1), k_max=lvl.ca_kmax)
+    y, _ = linear_fwd(att, wp, bp, residual=x, drop_p=drop_p, seed=seed)
+    return y, q, att, lse, kv
+
+
+def crossattn_branch_bwd(dy, n, q, kv, att, lse, wq, qn, kn, wp, lvl, H, p, seed, attn_p, hand, dkv=None, own=None):
+    """-> (dn, dwq, dbq, gq, bq, gk, bk, dwp, dbp) + own's (dwkv, dbkv, dctx).  d kv goes to `dkv`, an [L, 2C] view (a ProjBank
+    gradient slice): written by the attention backward itself when the level has one key-side slot, else summed into it by
+    lotus_sum_slabs_ld.  own = (context, wkv, d context wanted) instead: the slots are summed into a fresh tensor (lotus_sum_slabs;
+    one slot: the slab itself) and the kv products follow, in front of q's.  The composite entry points make the same choice of
+    reduce kernel per path (csrc/blocks.cpp); the two kernels need not round alike."""
+    N, C = n.shape
+    dz = _masked(dy, p, seed, hand)
+    dwp, dbp = linear_wgrad(dz, att)
+    datt = linear_dgrad(dz, wp)
+    dq = torch.empty(N, C, dtype=n.dtype, device=n.device)
+    G, L = lvl.ca_groups, kv.shape[0]
+    if own is not None or G > 1:
+        part = torch.empty(G, L, 2 * C, dtype=n.dtype, device=n.device)
+        tgt, tld, tps = part, 2 * C, L * 2 * C
+    else:
+        tgt, tld, tps = dkv, dkv.stride(0), 0
+    gq, bq, gk, bk = attention_bwd(q, C, 0, kv, kv.stride(0), 0, C, None, None, None, lvl.ca_tiles, lvl.ca_blocks, lvl.n_ca_blocks,
+                                   qn, kn, att, datt, lse, dq, C, 0, tgt, tld, 0, C, tps, 0, H, C // H, attn_p, mix_seed(seed, 1),
+                                   k_max=lvl.ca_kmax)
+    mine = ()
+    if own is not None:
+        context, wkv, want_dctx = own
+        dkv = sum_slabs(part)
+        mine = linear_wgrad(dkv, context) + (linear_dgrad(dkv, wkv) if want_dctx else None,)
+    elif G > 1:
+        call("lotus_sum_slabs_ld", part, dkv, L, 2 * C, dkv.stride(0), L * 2 * C, G)
+    dwq, dbq = linear_wgrad(dq, n)
+    dn = linear_dgrad(dq, wq)
+    return (dn, dwq, dbq, gq, bq, gk, bk, dwp, dbp) + mine
+
+
 class CpeFn(torch.autograd.Function):
     """x1 = x + LN(Linear(SubMConv3d_3(xs))).  In the encoder xs is x; in the decoder xs is the
     stale proj_skip branch (SURVEY.md Trap 3), hence two tensor inputs."""
@@ -1490,13 +1540,8 @@ class CrossAttnFn(torch.autograd.Function):
             ctx.save_for_backward(x, context, g, wq, wkv, qnw, qnb, knw, knb, wp, saved)
             return y
         n, mean, rstd = ln_fwd(x, g, b)
-        q, _ = linear_fwd(n, wqk, bq)
-        kv, _ = linear_fwd(context, wkvk, bkv)
-        att = torch.empty(N, C, dtype=x.dtype, device=x.device)
-        lse = torch.empty(N, H, dtype=torch.float32, device=x.device)
-        attention_fwd(q, C, 0, kv, 2 * C, 0, C, None, None, None, lvl.ca_tiles, lvl.n_ca_tiles, (qnw, qnb), (knw, knb),
-                      att, lse, H, d, attn_p, mix_seed(seed, 1), k_max=lvl.ca_kmax)
-        y, _ = linear_fwd(att, wpk, bp, residual=x, drop_p=drop_p, seed=seed)
+        y, q, att, lse, kv = crossattn_branch_fwd(n, x, wqk, bq, None, (qnw, qnb), (knw, knb), wpk, bp, lvl, H, drop_p, seed, attn_p,
+                                                  own=(context, wkvk, bkv))
         ctx.save_for_backward(x, context, g, wq, wkv, qnw, qnb, knw, knb, wp, n, q, kv, att, lse, mean, rstd)
         return y
 
@@ -1522,89 +1567,78 @@ class CrossAttnFn(torch.autograd.Function):
                            wss_bytes, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
             return (dx, dctx) + _grad_views(grads, "cross", C, H, Cc=Cc) + (None,) * 7
         x, context, g, wq, wkv, qnw, qnb, knw, knb, wp, n, q, kv, att, lse, mean, rstd = ctx.saved_tensors
-        N, C = x.shape
-        dev = x.device
-        dz = _masked(dy, p, seed, hand_in)
-        dwp, dbp = linear_wgrad(dz, att)
-        datt = linear_dgrad(dz, ctx.wk[2])
-        dq = torch.empty(N, C, dtype=x.dtype, device=dev)
-        G, L = lvl.ca_groups, kv.shape[0]
-        dkv_part = torch.empty(G, L, 2 * C, dtype=x.dtype, device=dev)
-        gq, bq_, gk, bk_ = attention_bwd(q, C, 0, kv, 2 * C, 0, C, None, None, None, lvl.ca_tiles, lvl.ca_blocks,
-                                         lvl.n_ca_blocks, (qnw, qnb), (knw, knb), att, datt, lse, dq, C, 0, dkv_part,
-                                         2 * C, 0, C, L * 2 * C, 0, H, d, attn_p, mix_seed(seed, 1), k_max=lvl.ca_kmax)
-        dkv = sum_slabs(dkv_part)
-        dwkv, dbkv = linear_wgrad(dkv, context)
-        dctx = linear_dgrad(dkv, ctx.wk[1]) if ctx.needs_input_grad[1] else None
-        dwq, dbq = linear_wgrad(dq, n)
-        dn = linear_dgrad(dq, ctx.wk[0])
+        dn, dwq, dbq, gq, bq_, gk, bk_, dwp, dbp, dwkv, dbkv, dctx = crossattn_branch_bwd(
+            dy, n, q, kv, att, lse, ctx.wk[0], (qnw, qnb), (knw, knb), ctx.wk[2], lvl, H, p, seed, attn_p, hand_in,
+            own=(context, ctx.wk[1], ctx.needs_input_grad[1]))
         dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy, hand=hand_out)
         return dx, dctx, dg, db, dwq, dbq, dwkv, dbkv, gq, bq_, gk, bk_, dwp, dbp, None, None, None, None, None, None, None
 
 
-class KvBank:
-    """The keys / values of every CABlock of one forward pass, projected together.  `kv` [L, sum 2C] holds
-    Linear(ctx -> 2C_b)(context) of block b in columns offs[b] : offs[b] + 2C_b; `dkv` (same shape, allocated by the first
-    backward that needs it) collects d kv of every block, each CrossAttnKvFn.backward writing its own column slice."""
-    __slots__ = ("kv", "dkv", "offs", "widths", "slices")
+class ProjBank:
+    """Projections of ONE shared context for every consumer of a forward pass (ProjAllFn): `slab` [rows, sum w_j] holds consumer
+    j's in columns offs[j] : offs[j] + widths[j] (`slices[j]`); `dslab` (same shape, allocated by the first backward that needs
+    it) collects the gradients, each consumer's backward writing its own column slice.  The consumers: the CABlocks (their keys /
+    values, ptv3) or the PDNorms ([shift | scale], adanorm)."""
+    __slots__ = ("slab", "dslab", "offs", "widths", "slices")
 
-    def slice(self, b):
-        return self.slices[b]
+    def slice(self, j):
+        return self.slices[j]
 
-    def grad_slice(self, b):
-        if self.dkv is None:
-            self.dkv = torch.empty_like(self.kv)
-        return self.dkv[:, self.offs[b]:self.offs[b] + self.widths[b]]
+    def grad_slice(self, j):
+        if self.dslab is None:
+            self.dslab = torch.empty_like(self.slab)
+        return self.dslab[:, self.offs[j]:self.offs[j] + self.widths[j]]
 
 
-class KvAllFn(torch.autograd.Function):
-    """kv_b = Linear(context; W_b, bias_b) for every CABlock b in ONE product (model_ca.py:46-67 evaluates the nine
-    [L, 256] x [256, 2C_b] products one by one, each 3 row tiles tall): context [L, Cc] x cat(W_b) [sum 2C_b, Cc].  The weights
-    stay the modules' own parameters (state_dict layout unchanged); their concatenation is one copy launch per step.
-    Returns the column slices (views of one slab).  Backward: one input-gradient and one weight-gradient product over the
-    shared d kv slab that the CrossAttnKvFn backward passes filled."""
+class ProjAllFn(torch.autograd.Function):
+    """slice_j = Linear_j(pre(context)) for every consumer j in ONE product, pre(context) [rows, Cc] x cat(W_j) [sum w_j, Cc];
+    pre = None, or "silu" (the PDNorm modulations).  model_ca.py:46-67 evaluates the nine [L, 256] x [256, 2C_b] kv products one
+    by one, each 3 row tiles tall; v1's 40 PDNorms are 24 064 columns.  The weights stay the modules' own parameters; their
+    concatenation is one copy launch per step.  Returns the column slices (views of one slab).  Backward: one weight-gradient and
+    one input-gradient product over the gradient slab that the consumers' backward passes filled."""
 
     @_fwd
-    def forward(ctx, context, bank, *wb):
+    def forward(ctx, context, bank, pre, *wb):
+        # (shadows, precision 5, exist under bf16 storage only; the AdaNorm models are fp32: "silu" always reads the masters)
+        assert pre is None or (pre == "silu" and not _capi.BF16), pre
         ws, bs = wb[0::2], wb[1::2]
         wks, _ = _wk(*ws)   # (bf16 storage with weight shadows: the concatenation of the shadows, half the copy)
         W = torch.cat(wks, 0)
         bias = torch.cat(bs, 0)
-        kv, _ = linear_fwd(context, W, bias)
-        bank.kv, bank.dkv = kv, None
+        s = silu(context) if pre else context
+        slab, _ = linear_fwd(s, W, bias)
+        bank.slab, bank.dslab = slab, None
         bank.widths = [w.shape[0] for w in ws]
         bank.offs = [0]
         for w_ in bank.widths[:-1]:
             bank.offs.append(bank.offs[-1] + w_)
-        bank.slices = tuple(kv[:, o:o + w_] for o, w_ in zip(bank.offs, bank.widths))
-        ctx.bank = bank
-        ctx.save_for_backward(context, W)
+        bank.slices = tuple(slab[:, o:o + w_] for o, w_ in zip(bank.offs, bank.widths))
+        ctx.bank, ctx.pre = bank, pre
+        ctx.save_for_backward(context, s, W)
         return bank.slices
 
     @_joined
     def backward(ctx, *gs):
-        context, W = ctx.saved_tensors
+        context, s, W = ctx.saved_tensors
         bank = ctx.bank
-        if bank.dkv is None:
-            bank.dkv = torch.empty_like(bank.kv)
-        dkv = bank.dkv
-        for b, g in enumerate(gs):  # normally every g IS its slice of the slab (written in place by the block's backward)
-            sl = dkv[:, bank.offs[b]:bank.offs[b] + bank.widths[b]]
+        for j, g in enumerate(gs):  # normally every g IS its slice of the slab (written in place by the consumer's backward)
+            sl = bank.grad_slice(j)
             if g is None:
                 sl.zero_()
             elif g.data_ptr() != sl.data_ptr() or g.stride() != sl.stride():
                 sl.copy_(g)
-        dW, db = linear_wgrad(dkv, context)
-        dctx = linear_dgrad(dkv, W) if ctx.needs_input_grad[0] else None
-        out = [dctx, None]
+        dslab = bank.dslab
+        dW, db = linear_wgrad(dslab, s)
+        dctx = linear_dgrad(dslab, W) if ctx.needs_input_grad[0] else None
+        out = [silu(context, dctx) if ctx.pre and dctx is not None else dctx, None, None]
         for o, w_ in zip(bank.offs, bank.widths):
             out += [dW[o:o + w_], db[o:o + w_]]
-        bank.dkv = None
+        bank.dslab = None
         return tuple(out)
 
 
 class CrossAttnKvFn(torch.autograd.Function):
-    """CrossAttnFn with the keys / values taken from a KvBank slice (projected once for all blocks by KvAllFn):
+    """CrossAttnFn with the keys / values taken from a ProjBank slice (projected once for all blocks by ProjAllFn):
     y = x + drop(proj(CrossAttention(q(LN(x)), kv)))   (model_ca.py:46-101, :135-140)."""
 
     @_fwd
@@ -1630,12 +1664,7 @@ class CrossAttnKvFn(torch.autograd.Function):
             ctx.save_for_backward(x, kv, g, wq, qnw, qnb, knw, knb, wp, saved)
             return y
         n, mean, rstd = ln_fwd(x, g, b)
-        q, _ = linear_fwd(n, wqk, bq)
-        att = torch.empty(N, C, dtype=x.dtype, device=x.device)
-        lse = torch.empty(N, H, dtype=torch.float32, device=x.device)
-        attention_fwd(q, C, 0, kv, kv_ld, 0, C, None, None, None, lvl.ca_tiles, lvl.n_ca_tiles, (qnw, qnb), (knw, knb),
-                      att, lse, H, d, attn_p, mix_seed(seed, 1), k_max=lvl.ca_kmax)
-        y, _ = linear_fwd(att, wpk, bp, residual=x, drop_p=drop_p, seed=seed)
+        y, q, att, lse, _ = crossattn_branch_fwd(n, x, wqk, bq, kv, (qnw, qnb), (knw, knb), wpk, bp, lvl, H, drop_p, seed, attn_p)
         ctx.save_for_backward(x, kv, g, wq, qnw, qnb, knw, knb, wp, n, q, att, lse, mean, rstd)
         return y
 
@@ -1660,25 +1689,8 @@ class CrossAttnKvFn(torch.autograd.Function):
                            wss, wss_bytes, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
             return (dx, dkv) + _grad_views(grads, "crosskv", C, H) + (None,) * 9
         x, kv, g, wq, qnw, qnb, knw, knb, wp, n, q, att, lse, mean, rstd = ctx.saved_tensors
-        N, C = x.shape
-        dev = x.device
-        dz = _masked(dy, p, seed, hand_in)
-        dwp, dbp = linear_wgrad(dz, att)
-        datt = linear_dgrad(dz, ctx.wk[1])
-        dq = torch.empty(N, C, dtype=x.dtype, device=dev)
-        G, L = lvl.ca_groups, kv.shape[0]
-        if G > 1:
-            dkv_part = torch.empty(G, L, 2 * C, dtype=x.dtype, device=dev)
-            tgt, tld, tps = dkv_part, 2 * C, L * 2 * C
-        else:
-            tgt, tld, tps = dkv, dkv.stride(0), 0
-        gq, bq_, gk, bk_ = attention_bwd(q, C, 0, kv, kv.stride(0), 0, C, None, None, None, lvl.ca_tiles, lvl.ca_blocks,
-                                         lvl.n_ca_blocks, (qnw, qnb), (knw, knb), att, datt, lse, dq, C, 0, tgt, tld, 0, C, tps, 0, H, d,
-                                         attn_p, mix_seed(seed, 1), k_max=lvl.ca_kmax)
-        if G > 1:
-            call("lotus_sum_slabs_ld", dkv_part, dkv, L, 2 * C, dkv.stride(0), L * 2 * C, G)
-        dwq, dbq = linear_wgrad(dq, n)
-        dn = linear_dgrad(dq, ctx.wk[0])
+        dn, dwq, dbq, gq, bq_, gk, bk_, dwp, dbp = crossattn_branch_bwd(
+            dy, n, q, kv, att, lse, ctx.wk[0], (qnw, qnb), (knw, knb), ctx.wk[1], lvl, H, p, seed, attn_p, hand_in, dkv=dkv)
         dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy, hand=hand_out)
         return (dx, dkv, dg, db, dwq, dbq, gq, bq_, gk, bk_, dwp, dbp) + (None,) * 9
 
@@ -1737,7 +1749,7 @@ class PairFn(torch.autograd.Function):
     the launches of CpeFn -> SelfAttnFn -> FfnFn -> CrossAttnKvFn -> FfnFn in the same order on the same streams
     (bit-identical, tests/test_gpu_round4.py), one Python -> C transition and one set of buffers per direction.
     Inputs: x, xs (x itself in the encoder, the stale skip branch for the first Block of a decoder stage), the block's
-    KvBank slice, the packed convolution weights, the 38 parameters in _PAIR_PARAM_SLOTS order, and a meta tuple."""
+    ProjBank slice, the packed convolution weights, the 38 parameters in _PAIR_PARAM_SLOTS order, and a meta tuple."""
 
     @_fwd
     def forward(ctx, x, xs, kv, wt, *rest):
@@ -1930,6 +1942,49 @@ class LinearFn(torch.autograd.Function):
         return dx, dw, (db if ctx.needs_input_grad[2] else None)
 
 
+def cloud_max_fwd(x, lvl):
+    """-> (pc [B, C] = torch.stack([torch.max(x, 0)[0] for x in torch.split(feat, npoints_in_batch)]), simple_policy_ptv3.py:117-119
+    / motion_planner_ptv3.py:117-119; arg [B, C] int32 = the row each maximum came from, test taps applied)."""
+    B, C = len(lvl.counts), x.shape[1]
+    pc = torch.empty(B, C, dtype=x.dtype, device=x.device)
+    arg = torch.empty(B, C, dtype=torch.int32, device=x.device)
+    ws = _ws(query("lotus_cloud_max_workspace", B, C), x.device)
+    call("lotus_cloud_max_fwd", x, lvl.off, B, C, pc, arg, ws, ws.numel())
+    if ARG_TAP is not None or ARG_INJECT:
+        arg = _arg_hook("cloud", arg)
+    return pc, arg
+
+
+def head_trunk_fwd(x, hw0, hb0, aw0, ab0, aw3, ab3, lvl, drop_p, seed, heat):
+    """What every ActionHead computes (simple_policy_ptv3.py:113-120): the hidden heat-map layer h, the per-cloud max, the action
+    MLP; heat(h) = the node's own second heat-map layer, launched right behind h.  -> (h, hpre, heat(h), pc, arg, a, apre, ae)."""
+    h, hpre = linear_fwd(x, hw0, hb0, act=ACT_LEAKY, save_pre=True, drop_p=drop_p, seed=seed)
+    if ARG_TAP is not None or ARG_INJECT:
+        hpre = _arg_hook("leaky", hpre)
+    pos = heat(h)
+    pc, arg = cloud_max_fwd(x, lvl)
+    a, apre = linear_fwd(pc, aw0, ab0, act=ACT_LEAKY, save_pre=True, drop_p=drop_p, seed=mix_seed(seed, 1))
+    ae, _ = linear_fwd(a, aw3, ab3)
+    return h, hpre, pos, pc, arg, a, apre, ae
+
+
+def head_trunk_bwd(dae_o, dxt, x, hw0, hw3, aw0, aw3, h, hpre, pc, arg, a, apre, lvl, p, seed):
+    """dae_o = d ae, dxt = d heat(h) -> (dx, dhw0, dhb0, dhw3, dhb3, daw0, dab0, daw3, dab3), the head nodes' argument order."""
+    # action branch (B rows)
+    daw3, dab3 = linear_wgrad(dae_o, a)
+    dapre = linear_dgrad(dae_o, aw3, pre=apre, act=ACT_LEAKY, drop_p=p, seed=mix_seed(seed, 1))
+    daw0, dab0 = linear_wgrad(dapre, pc)
+    dpc = linear_dgrad(dapre, aw0)
+    # heatmap branch (N rows)
+    dhw3, dhb3 = linear_wgrad(dxt, h)
+    dhpre = linear_dgrad(dxt, hw3, pre=hpre, act=ACT_LEAKY, drop_p=p, seed=seed)
+    dhw0, dhb0 = linear_wgrad(dhpre, x)
+    dxh = linear_dgrad(dhpre, hw0)
+    dx = torch.empty_like(x)
+    call("lotus_cloud_max_bwd", dpc, arg, lvl.batch, x.shape[0], x.shape[1], dxh, dx)
+    return dx, dhw0, dhb0, dhw3, dhb3, daw0, dab0, daw3, dab3
+
+
 class HeadLossFn(torch.autograd.Function):
     """ActionHead (heatmap_disc / max / euler_disc) + compute_loss, simple_policy_ptv3.py:113-157,
     :308-373.  Returns (losses[4] = pos, rot, open, total; xt [N, 3*2*pos_bins]; ae [B, 217])."""
@@ -1937,20 +1992,9 @@ class HeadLossFn(torch.autograd.Function):
     @_fwd
     def forward(ctx, x, hw0, hb0, hw3, hb3, aw0, ab0, aw3, ab3, lvl, tgt, gt, pos_w, rot_w, drop_p, seed, with_loss):
         dev = x.device
-        N, C = x.shape
         B = len(lvl.counts)
-        h, hpre = linear_fwd(x, hw0, hb0, act=ACT_LEAKY, save_pre=True, drop_p=drop_p, seed=seed)
-        xt, _ = linear_fwd(h, hw3, hb3)
-        if ARG_TAP is not None or ARG_INJECT:
-            hpre = _arg_hook("leaky", hpre)
-        pc = torch.empty(B, C, dtype=x.dtype, device=dev)
-        arg = torch.empty(B, C, dtype=torch.int32, device=dev)
-        ws = _ws(query("lotus_cloud_max_workspace", B, C), x.device)
-        call("lotus_cloud_max_fwd", x, lvl.off, B, C, pc, arg, ws, ws.numel())
-        if ARG_TAP is not None or ARG_INJECT:
-            arg = _arg_hook("cloud", arg)
-        a, apre = linear_fwd(pc, aw0, ab0, act=ACT_LEAKY, save_pre=True, drop_p=drop_p, seed=mix_seed(seed, 1))
-        ae, _ = linear_fwd(a, aw3, ab3)
+        h, hpre, xt, pc, arg, a, apre, ae = head_trunk_fwd(x, hw0, hb0, aw0, ab0, aw3, ab3, lvl, drop_p, seed,
+                                                           lambda h: linear_fwd(h, hw3, hb3)[0])
         losses = torch.zeros(4, dtype=torch.float32, device=dev)
         nb = xt.shape[1] // 3
         nrot = (ae.shape[1] - 1) // 3
@@ -1969,27 +2013,11 @@ class HeadLossFn(torch.autograd.Function):
         x, hw0, hw3, aw0, aw3, h, hpre, xt, pc, arg, a, apre, stats, dae, tgt = ctx.saved_tensors
         lvl, pos_w, rot_w, p, seed, with_loss, nb, nrot = ctx.meta
         assert with_loss, "backward through the head requires compute_loss=True"
-        dev = x.device
-        N, C = x.shape
-        B = len(lvl.counts)
-        gl = gl.contiguous()
         dxt = torch.empty_like(xt)
-        dae_o = torch.empty(dae.shape, dtype=xt.dtype, device=dev)
-        call("lotus_loss_bwd", xt, tgt, lvl.off, lvl.batch, stats, dae, gl, float(pos_w), float(rot_w), B, N, nb, nrot,
-             dxt, dae_o)
-        # action branch (B rows)
-        daw3, dab3 = linear_wgrad(dae_o, a)
-        dapre = linear_dgrad(dae_o, aw3, pre=apre, act=ACT_LEAKY, drop_p=p, seed=mix_seed(seed, 1))
-        daw0, dab0 = linear_wgrad(dapre, pc)
-        dpc = linear_dgrad(dapre, aw0)
-        # heatmap branch (N rows)
-        dhw3, dhb3 = linear_wgrad(dxt, h)
-        dhpre = linear_dgrad(dxt, hw3, pre=hpre, act=ACT_LEAKY, drop_p=p, seed=seed)
-        dhw0, dhb0 = linear_wgrad(dhpre, x)
-        dxh = linear_dgrad(dhpre, hw0)
-        dx = torch.empty_like(x)
-        call("lotus_cloud_max_bwd", dpc, arg, lvl.batch, N, C, dxh, dx)
-        return (dx, dhw0, dhb0, dhw3, dhb3, daw0, dab0, daw3, dab3) + (None,) * 8
+        dae_o = torch.empty(dae.shape, dtype=xt.dtype, device=x.device)
+        call("lotus_loss_bwd", xt, tgt, lvl.off, lvl.batch, stats, dae, gl.contiguous(), float(pos_w), float(rot_w), len(lvl.counts),
+             x.shape[0], nb, nrot, dxt, dae_o)
+        return head_trunk_bwd(dae_o, dxt, x, hw0, hw3, aw0, aw3, h, hpre, pc, arg, a, apre, lvl, p, seed) + (None,) * 8
 
 
 ROT_KINDS = {"euler_disc": 0, "euler": 1, "quat": 2}  # rot_kind of lotus_reg_loss_fwd
@@ -2028,25 +2056,13 @@ class RegHeadLossFn(torch.autograd.Function):
                 drop_p, seed, with_loss):
         assert not _capi.BF16, "the regression head runs with fp32 activation storage"
         dev = x.device
-        N, C = x.shape
         B = len(lvl.counts)
         mlp, kind = pos_type == "heatmap_mlp", ROT_KINDS[rot_type]
-        h, hpre = linear_fwd(x, hw0, hb0, act=ACT_LEAKY, save_pre=True, drop_p=drop_p, seed=seed)
-        if ARG_TAP is not None or ARG_INJECT:
-            hpre = _arg_hook("leaky", hpre)
-        e = stats = None
-        if mlp:
-            e, xt, stats = softpos_fwd(h, hw3, hb3, pc_fts, lvl, temp)
+        if mlp:   # -> (e, xt, stats)
+            heat = lambda h: softpos_fwd(h, hw3, hb3, pc_fts, lvl, temp)  # noqa: E731
         else:
-            xt, _ = linear_fwd(h, hw3, hb3)
-        pc = torch.empty(B, C, dtype=x.dtype, device=dev)
-        arg = torch.empty(B, C, dtype=torch.int32, device=dev)
-        ws = _ws(query("lotus_cloud_max_workspace", B, C), x.device)
-        call("lotus_cloud_max_fwd", x, lvl.off, B, C, pc, arg, ws, ws.numel())
-        if ARG_TAP is not None or ARG_INJECT:
-            arg = _arg_hook("cloud", arg)
-        a, apre = linear_fwd(pc, aw0, ab0, act=ACT_LEAKY, save_pre=True, drop_p=drop_p, seed=mix_seed(seed, 1))
-        ae, _ = linear_fwd(a, aw3, ab3)
+            heat = lambda h: (None, linear_fwd(h, hw3, hb3)[0], None)  # noqa: E731
+        h, hpre, (e, xt, stats), pc, arg, a, apre, ae = head_trunk_fwd(x, hw0, hb0, aw0, ab0, aw3, ab3, lvl, drop_p, seed, heat)
         W = ae.shape[1]
         nb = 0 if mlp else xt.shape[1] // 3
         nrot = (W - 1) // 3 if kind == 0 else 0
@@ -2076,31 +2092,17 @@ class RegHeadLossFn(torch.autograd.Function):
         x, hw0, hw3, aw0, aw3, h, hpre, xt, pc, arg, a, apre, dae, dpos, pc_fts, e, stats, ce, tgt = ctx.saved_tensors
         lvl, pos_w, rot_w, p, seed, with_loss, mlp, nb, temp = ctx.meta
         assert with_loss, "backward through the head requires compute_loss=True"
-        dev = x.device
-        N, C = x.shape
         B, W = dae.shape
-        gl = gl.contiguous()
         dae_o = torch.empty_like(dae)
         gpos = torch.empty_like(dpos)
-        call("lotus_reg_loss_bwd", dae, dpos, gl, float(pos_w), float(rot_w), B, W, dae_o, gpos)
-        # action branch (B rows)
-        daw3, dab3 = linear_wgrad(dae_o, a)
-        dapre = linear_dgrad(dae_o, aw3, pre=apre, act=ACT_LEAKY, drop_p=p, seed=mix_seed(seed, 1))
-        daw0, dab0 = linear_wgrad(dapre, pc)
-        dpc = linear_dgrad(dapre, aw0)
-        # heatmap branch (N rows): d e [N, 4] of the soft position, or d xt of the heat-map cross entropy
+        call("lotus_reg_loss_bwd", dae, dpos, gl.contiguous(), float(pos_w), float(rot_w), B, W, dae_o, gpos)
+        # d e [N, 4] of the soft position, or d xt of the heat-map cross entropy
         if mlp:
             dxt = softpos_bwd(gpos, e, pc_fts, lvl, stats, xt, temp)
         else:
             dxt = torch.empty_like(xt)
-            call("lotus_pos_ce_bwd", xt, tgt, lvl.off, lvl.batch, ce, gpos, B, N, nb, dxt)
-        dhw3, dhb3 = linear_wgrad(dxt, h)
-        dhpre = linear_dgrad(dxt, hw3, pre=hpre, act=ACT_LEAKY, drop_p=p, seed=seed)
-        dhw0, dhb0 = linear_wgrad(dhpre, x)
-        dxh = linear_dgrad(dhpre, hw0)
-        dx = torch.empty_like(x)
-        call("lotus_cloud_max_bwd", dpc, arg, lvl.batch, N, C, dxh, dx)
-        return (dx, dhw0, dhb0, dhw3, dhb3, daw0, dab0, daw3, dab3) + (None,) * 12
+            call("lotus_pos_ce_bwd", xt, tgt, lvl.off, lvl.batch, ce, gpos, B, x.shape[0], nb, dxt)
+        return head_trunk_bwd(dae_o, dxt, x, hw0, hw3, aw0, aw3, h, hpre, pc, arg, a, apre, lvl, p, seed) + (None,) * 12
 
 
 class StepHeadFn(torch.autograd.Function):
@@ -2272,18 +2274,11 @@ class TrajRegLossFn(torch.autograd.Function):
 
 
 class CloudMaxFn(torch.autograd.Function):
-    """torch.stack([torch.max(x, 0)[0] for x in torch.split(feat, npoints_in_batch)]),
-    motion_planner_ptv3.py:117-119 / simple_policy_ptv3.py:117-119."""
+    """cloud_max_fwd as a node of its own (the motion planner's action branch)."""
 
     @_fwd
     def forward(ctx, x, lvl):
-        B, C = len(lvl.counts), x.shape[1]
-        y = torch.empty(B, C, dtype=x.dtype, device=x.device)
-        arg = torch.empty(B, C, dtype=torch.int32, device=x.device)
-        ws = _ws(query("lotus_cloud_max_workspace", B, C), x.device)
-        call("lotus_cloud_max_fwd", x, lvl.off, B, C, y, arg, ws, ws.numel())
-        if ARG_TAP is not None or ARG_INJECT:
-            arg = _arg_hook("cloud", arg)
+        y, arg = cloud_max_fwd(x, lvl)
         ctx.save_for_backward(arg)
         ctx.lvl, ctx.n = lvl, x.shape[0]
         return y

@@ -83,7 +83,7 @@ class Block(nn.Module):
         (ops.Handoff; the blocks of a stage form a chain with a single consumer each).  `lvl` carries the patch tables of
         this block's curve slot (Level.for_order); dpath = DropPath rate of the attention and MLP branches (training).
         The walker of Block, concat.PlainBlock and adanorm.AdaBlock: attn.q_norm / k_norm may be nn.Identity, and with `mods`
-        (the slices of the adanorm.ModBank `bank`, pid = id(PDNorm) -> slice index) the three norms are PDNorms.  Hand-overs exist
+        (the slices of the ops.ProjBank `bank`, pid = id(PDNorm) -> slice index) the three norms are PDNorms.  Hand-overs exist
         for plain LayerNorms with q/k norm only."""
         def site(n):  # a norm module -> (weight, bias), the nodes' trailing (mod, bank, j)
             if mods is None:
@@ -118,7 +118,7 @@ class CABlock(nn.Module):
         self.mlp = nn.Sequential(_MLP(c, int(c * mlp_ratio)))
 
     def run(self, x, context, lvl, drop_p, seed, attn_p=0.0, prev_hand=None, bank=None, bidx=0):
-        """bank / bidx: the keys / values of this block come from slice `bidx` of an ops.KvBank (all CABlocks projected
+        """bank / bidx: the keys / values of this block come from slice `bidx` of an ops.ProjBank (all CABlocks projected
         together at the top of the forward pass) instead of this block's own product over the context."""
         a, n1 = self.attn, self.norm1[0]
         h_attn = ops.Handoff()
@@ -174,7 +174,7 @@ class PointDict(dict):
 
 class _Pass:
     """What one forward pass hands to its per-stage steps: the levels, the dropout rates of this pass, the packed convolution
-    weights per Block, the context and the class's bank (ops.KvBank | adanorm.ModBank; `mods` = the ModBank's slices)."""
+    weights per Block, the context and its ops.ProjBank (the CABlocks' kv | the PDNorms' modulations, `mods` = its slices)."""
     __slots__ = ("levels", "training", "p", "pa", "packs", "context", "bank", "mods")
 
 
@@ -292,7 +292,7 @@ class PointTransformerV3CA(nn.Module):
 
     def _index_sites(self):
         # every CABlock in execution order (module order = encoder stages, then decoder stages as they run): their kv
-        # projections of the shared context are evaluated as one product at the top of forward (ops.KvAllFn)
+        # projections of the shared context are evaluated as one product at the top of forward (ops.ProjAllFn)
         self._cablocks = [m for m in self.modules() if isinstance(m, CABlock)]
         self._cab_index = {id(m): i for i, m in enumerate(self._cablocks)}
         self.kv_group = os.environ.get("LOTUS_KV_GROUP", "1") != "0"
@@ -488,11 +488,11 @@ class PointTransformerV3CA(nn.Module):
         fw.bank = None
         self._pair_on = False  # decided per stage (_enter_stage): ops.pair_enabled(points of the stage's level)
         if self.kv_group and fw.context is not None and len(self._cablocks) > 1:
-            fw.bank = ops.KvBank()
+            fw.bank = ops.ProjBank()
             wb = []
             for c in self._cablocks:
                 wb += [c.attn.kv.weight, c.attn.kv.bias]
-            ops.KvAllFn.apply(fw.context, fw.bank, *wb)
+            ops.ProjAllFn.apply(fw.context, fw.bank, None, *wb)
         return x
 
     def _enter_stage(self, fw, lvl):

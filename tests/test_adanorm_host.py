@@ -132,15 +132,19 @@ def test_mean_reduce_needs_one_token_per_cloud():
 
 def test_one_set_of_norm_site_nodes():
     """The CA, AdaNorm and Concat backbones reach their stem, pooling, unpooling and Block sub-blocks through the six nodes of
-    ops.py and one block walker: adanorm.py and concat.py define no autograd node besides the modulation product and the two stems
-    with a pre-norm convolution of their own, and ops.py (which holds both norm families) does not import adanorm.py."""
+    ops.py and one block walker: adanorm.py and concat.py define no autograd node besides the two stems with a pre-norm convolution
+    of their own — the modulation product is ops.ProjAllFn over an ops.ProjBank, the node and bank of the CABlocks' keys / values,
+    under no other name — and ops.py (which holds both norm families) does not import adanorm.py."""
     from robot_3dlotus_amd import adanorm, concat, ops, ptv3
 
     def nodes(mod):
         return {n for n, c in vars(mod).items()
                 if isinstance(c, type) and issubclass(c, torch.autograd.Function) and c.__module__ == mod.__name__}
 
-    assert nodes(adanorm) == {"ModAllFn", "StemGroupsFn"}
+    assert nodes(adanorm) == {"StemGroupsFn"}
+    assert issubclass(ops.ProjAllFn, torch.autograd.Function) and isinstance(ops.ProjBank, type)
+    for old in ("KvBank", "KvAllFn", "ModBank", "ModAllFn"):
+        assert not hasattr(ops, old) and not hasattr(adanorm, old), old
     assert nodes(concat) == {"CtxStemFn"}
     assert {"StemFn", "PoolFn", "UnpoolFn", "CpeFn", "SelfAttnFn", "FfnFn"} <= nodes(ops)
     assert adanorm.AdaBlock.run is ptv3.Block.run and concat.PlainBlock.run is ptv3.Block.run

@@ -191,14 +191,14 @@ def test_adabn_kernels_against_float64(C, layout, training):
 
 
 def test_silu_and_modulation_product():
-    from robot_3dlotus_amd import adanorm as an
+    from robot_3dlotus_amd import ops
 
     c = torch.randn(5, 256, device="cuda", requires_grad=True)
     ws = [torch.randn(2 * C, 256, device="cuda", requires_grad=True) * 0.05 for C in (64, 128)]
     ws = [w.detach().requires_grad_() for w in ws]
     bs = [torch.randn(w.shape[0], device="cuda", requires_grad=True) for w in ws]
-    bank = an.ModBank()
-    outs = an.ModAllFn.apply(c, bank, ws[0], bs[0], ws[1], bs[1])
+    bank = ops.ProjBank()
+    outs = ops.ProjAllFn.apply(c, bank, "silu", ws[0], bs[0], ws[1], bs[1])
     cd = c.detach().double().requires_grad_()
     wd = [w.detach().double().requires_grad_() for w in ws]
     bd = [b.detach().double().requires_grad_() for b in bs]

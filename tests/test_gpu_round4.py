@@ -1,6 +1,6 @@
 """Round-4 restructuring of the step, each piece against the path it replaces:
 
-* ops.KvAllFn / CrossAttnKvFn — the kv projections of all CABlocks as ONE product over the shared context
+* ops.ProjAllFn / CrossAttnKvFn — the kv projections of all CABlocks as ONE product over the shared context
   (/root/reference/genrobo3d/models/PointTransformerV3/model_ca.py:46-67 evaluates one small product per block): composite
   entry point vs per-launch host path bit-identical, whole model vs the per-block projection path to fp32 summation noise;
 * the one-launch BatchNorm statistics (last-arrival reduction, csrc/norm.hip) vs the three-launch path and vs float64."""
@@ -68,7 +68,7 @@ def _levels():
 @pytest.mark.parametrize("join", ["node", "end"])
 @pytest.mark.parametrize("C,H", [(64, 2), (256, 8)])
 def test_crossattn_kv_composite_is_bit_identical_and_matches_own_projection(C, H, join):
-    """CrossAttnKvFn (kv from a KvBank of three differently sized 'blocks') — composite C call vs per-launch host path bit for
+    """CrossAttnKvFn (kv from a ProjBank of three differently sized 'blocks') — composite C call vs per-launch host path bit for
     bit, both weight-gradient join modes, dropout and hand-overs on; and the same numbers as CrossAttnFn computing its own
     projection of the context (identical kernels, the kv product only tiled over a wider output)."""
     ops = _ops()
@@ -90,8 +90,8 @@ def test_crossattn_kv_composite_is_bit_identical_and_matches_own_projection(C, H
     def run_bank(composite):
         ops.set_composites(composite)
         x, ctxt, ps, kvw, dy = tensors()
-        bank = ops.KvBank()
-        sl = ops.KvAllFn.apply(ctxt, bank, *[t for pair in kvw for t in pair])
+        bank = ops.ProjBank()
+        sl = ops.ProjAllFn.apply(ctxt, bank, None, *[t for pair in kvw for t in pair])
         h_in, h_out = ops.Handoff(), ops.Handoff()
         h_out.arm(0.1, 99)
         y = ops.CrossAttnKvFn.apply(x, sl[1], *ps, lvl, H, 0.1, 777, 0.1, h_in, h_out, bank, 1)
@@ -126,6 +126,78 @@ def test_crossattn_kv_composite_is_bit_identical_and_matches_own_projection(C, H
     for i, (a, b) in enumerate(zip(mine, own)):
         scale = float(b.abs().max()) + 1e-12
         assert float((a - b).abs().max()) <= 2e-6 * scale, (i, float((a - b).abs().max()), scale)
+
+
+@pytest.mark.parametrize("pre,rows", [("silu", 3), (None, 5)])
+def test_proj_all_backward_fills_its_gradient_slab(pre, rows, monkeypatch):
+    """ProjAllFn.backward over three slices of unequal widths, one per rule: slice 0 is written in place through
+    bank.grad_slice and handed back as that very view (nothing to copy: the slab the consumer wrote is the operand of the two
+    products), slice 1 goes through an ordinary op (its gradient is copied in), slice 2 is unused (zero).  The consumer of
+    slice 0 poisons the rest of the fresh slab, so a slice that is neither copied nor zeroed shows.  Slices, d context and every
+    dW_j / db_j against float64 at the bar of the dense products (tests/dense_run.py); two runs agree bit for bit."""
+    ops = _ops()
+    F = torch.nn.functional
+    Cc, widths = 32, (8, 24, 16)
+    g = torch.Generator().manual_seed(rows)
+    c0 = torch.randn(rows, Cc, generator=g)
+    wb0 = [(torch.randn(w, Cc, generator=g) / Cc ** 0.5, torch.randn(w, generator=g)) for w in widths]
+    up = [torch.randn(rows, w, generator=g) for w in widths[:2]]
+    seen = {}
+
+    class InPlace(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, s, bank, j, u):
+            ctx.bank, ctx.j, ctx.u = bank, j, u
+            return (s * u).sum()
+
+        @staticmethod
+        def backward(ctx, go):
+            d = ctx.bank.grad_slice(ctx.j)       # the first touch: allocates the slab
+            ctx.bank.dslab.fill_(float("nan"))
+            d.copy_(ctx.u * go)
+            seen["slab"], seen["slice"] = ctx.bank.dslab, d
+            return d, None, None, None
+
+    wgrad = ops.linear_wgrad
+
+    def spy(dy, x, *a, **k):
+        seen["operand"] = dy
+        return wgrad(dy, x, *a, **k)
+
+    monkeypatch.setattr(ops, "linear_wgrad", spy)
+
+    def run():
+        seen.clear()
+        c = c0.cuda().requires_grad_(True)
+        wb = [(w.cuda().requires_grad_(True), b.cuda().requires_grad_(True)) for w, b in wb0]
+        bank = ops.ProjBank()
+        sl = ops.ProjAllFn.apply(c, bank, pre, *[t for pair in wb for t in pair])
+        assert bank.offs == [0, 8, 32] and bank.widths == list(widths) and all(bank.slice(j) is sl[j] for j in range(3))
+        assert [tuple(s.shape) for s in sl] == [(rows, w) for w in widths] and all(s.data_ptr() == bank.slab[:, o:].data_ptr()
+                                                                                   for s, o in zip(sl, bank.offs))
+        (InPlace.apply(sl[0], bank, 0, up[0].cuda()) + (sl[1] * up[1].cuda()).sum()).backward()
+        torch.cuda.synchronize()
+        # the no-copy rule: the slab that the consumer wrote in place is what was multiplied, and its slice is untouched
+        assert seen["operand"] is seen["slab"] and bank.dslab is None
+        assert seen["slice"].data_ptr() == seen["slab"].data_ptr() and torch.equal(seen["slice"], up[0].cuda())
+        assert torch.equal(seen["slab"][:, 8:32], up[1].cuda()) and not bool(seen["slab"][:, 32:].any())   # copied; zero
+        return [s.detach().clone() for s in sl] + [c.grad.clone()] + [t.grad.clone() for pair in wb for t in pair]
+
+    got, again = run(), run()
+    assert all(torch.equal(a, b) for a, b in zip(got, again))
+    cd = c0.double().requires_grad_(True)
+    wd = [(w.double().requires_grad_(True), b.double().requires_grad_(True)) for w, b in wb0]
+    s = F.silu(cd) if pre == "silu" else cd
+    ref = [F.linear(s, w, b) for w, b in wd]
+    ((ref[0] * up[0].double()).sum() + (ref[1] * up[1].double()).sum()).backward()
+    assert wd[2][0].grad is None and wd[2][1].grad is None
+    assert not bool(got[8].any()) and not bool(got[9].any())                     # the unused slice: dW_2 = db_2 = 0, exactly
+    want = [r.detach() for r in ref] + [cd.grad] + [t.grad if t.grad is not None else torch.zeros_like(t) for pair in wd for t in pair]
+    reds = [Cc] * 3 + [sum(widths)] + [rows] * 6                                   # reduction length of each product
+    for i, (a, b, red) in enumerate(zip(got, want, reds)):
+        err = float((a.double().cpu() - b).abs().max()) / max(1.0, float(b.abs().max()))
+        print(f"    output {i}: err {err:.3e}  bar {4e-7 * red ** 0.5 + 1e-6:.3e}")
+        assert a.shape == b.shape and err <= 4e-7 * red ** 0.5 + 1e-6, (i, err)
 
 
 @pytest.mark.parametrize("preset,n", [("tiny", 700), ("v1", 900)])

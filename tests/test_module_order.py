@@ -1,6 +1,6 @@
 """Registration ORDER of modules, parameters and state_dict entries of every preset, pinned against a fixture.
 
-The gradient reducer's buckets, the optimizer's parameter groups, the slice order of adanorm.ModBank, ops.WeightShadows and
+The gradient reducer's buckets, the optimizer's parameter groups, the slice order of the PDNorms' ops.ProjBank, ops.WeightShadows and
 checkpoints all depend on the order in which sub-modules are registered, not only on the set of their names.  The fixture
 tests/golden/module_order.json was written at the commit BEFORE the backbone constructors were split into overridable steps, by
 

@@ -179,6 +179,51 @@ def test_planner_refusals():
         MotionPlannerPTV3AdaNorm(bad)
 
 
+# ------------------------------------------------------------------------------------ one forward, one prefetch memory
+def test_one_planner_forward():
+    """The AdaNorm planner runs MotionPlannerPTV3CA's _forward; the soft head lives in the three steps it overrides."""
+    assert MotionPlannerPTV3AdaNorm._forward is MotionPlannerPTV3CA._forward
+    for step in ("_positions", "_pos_loss_term", "_final_positions"):
+        assert getattr(MotionPlannerPTV3AdaNorm, step) is not getattr(MotionPlannerPTV3CA, step), step
+    assert MotionPlannerPTV3AdaNorm._traj_losses is MotionPlannerPTV3CA._traj_losses
+
+
+def test_prefetch_memory_matches_by_identity_keeps_two_and_forgets_what_it_handed_out():
+    from robot_3dlotus_amd.motion_planner import _Prefetched
+
+    def batch(i):
+        return {"pc_fts": torch.full((3, 4), float(i)), "pc_labels": torch.zeros(3, dtype=torch.long)}
+
+    pre, b = _Prefetched(), [batch(i) for i in range(4)]
+    assert pre.take(b[0]) is None and pre.entries == []
+    built = [object() for _ in b]
+    pre.remember(b[0], built[0])
+    # an equal batch that is not the same tensors is another batch; so is one that shares only one of the two tensors
+    assert pre.take({k: v.clone() for k, v in b[0].items()}) is None
+    assert pre.take(dict(b[0], pc_labels=b[0]["pc_labels"].clone())) is None
+    assert pre.take(dict(b[0], pc_fts=b[0]["pc_fts"].clone())) is None
+    assert pre.take(b[0]) is built[0]
+    assert pre.take(b[0]) is None and pre.entries == []                     # consumed: forgotten
+    for i in range(3):
+        pre.remember(b[i], built[i])
+    assert len(pre.entries) == 2 and pre.take(b[0]) is None                 # at most two: the oldest is gone
+    assert len(pre.entries) == 1 and pre.entries[0][2] is built[2]          # a miss keeps the latest entry only
+    pre.remember(b[3], built[3])
+    assert pre.take(b[2]) is built[2] and len(pre.entries) == 1
+    assert pre.take(b[3]) is built[3] and pre.entries == []
+    # both planners use it, for what each of them builds: [pc | one-hot] as one tensor, or the two column groups
+    for cls, preset in ((MotionPlannerPTV3CA, "mp_tiny"), (MotionPlannerPTV3AdaNorm, "mp_ada_tiny")):
+        m = cls(lcfg.preset(preset))
+        assert isinstance(m._pre, _Prefetched)
+        got = m._point_input(b[1])
+        if cls is MotionPlannerPTV3CA:
+            assert got.shape == (3, 8) and got.dtype == torch.float32
+        else:
+            assert [tuple(t.shape) for t in got] == [(3, 4), (3, 4)]
+        m._pre.remember(b[1], got)
+        assert m._pre.take(b[1]) is got
+
+
 # ------------------------------------------------------------------------------------ the C-ABI: refusals and workspace sizes
 def _buf(nfloat, dtype=np.float32):
     a = np.zeros(nfloat + 8, dtype=dtype)
