@@ -349,7 +349,10 @@ size_t lotus_attention_bwd_workspace(int nblocks, int H);
  * buffer [n_extra][2*H*d] and are added to their point afterwards (no atomics, no zero-fill of dkv).
  * qn_w, qn_b, kn_w, kn_b ALL null: backward of the attention without q/k normalisation (rules as at lotus_attention_fwd).
  * dq / dk are then the plain products; dqn_w, dqn_b, dkn_w, dkn_b are not written and may be null, and no workspace is
- * used (workspace null / workspace_bytes 0 are fine). */
+ * used (workspace null / workspace_bytes 0 are fine).
+ * atomic_out: 0 = every (part_slot, key row, head) of dkv is written once with plain stores (what the model uses);
+ * 1 = the k / v gradients are atomically ADDED into dkv, which the caller has zeroed — fp32 storage only: the bf16 kernels have
+ * no atomic add, so the lotus_b16_ twin returns LOTUS_E_ARG for atomic_out != 0 and says so. */
 int lotus_attention_bwd(const lotus_act_t* q, long q_ld, int q_off, const lotus_act_t* kv, long kv_ld, int k_off, int v_off,
                         const int* qidx, const int* kidx, const int* owner, const int* tiles, const int* blocks,
                         int nblocks, const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b,
@@ -358,6 +361,22 @@ int lotus_attention_bwd(const lotus_act_t* q, long q_ld, int q_off, const lotus_
                         int atomic_out, const int* kext, const int* ext_pos, int n_extra, lotus_act_t* dkv_extra, float* dqn_w, float* dqn_b, float* dkn_w, float* dkn_b, int accumulate,
                         int H, int d, float scale, float eps, float drop_p, unsigned long long drop_seed,
                         int precision, int k_max, void* workspace, size_t workspace_bytes, void* stream);
+/* Diagnostic: the kernel the calling thread's last attention launch (lotus_attention_fwd / _bwd; also inside the composite
+ * entry points) was given to, recorded where the kernel is chosen and before the launch is attempted (so it is there after a
+ * launch that failed, too).  A call that launches nothing (an argument refusal, ntiles == 0, nblocks == 0) leaves the record as
+ * it was.  out[8] = {family, direction, targ, precision, norm, threads, lds_bytes, tail}:
+ *   family    1 attn_fwd_kernel (128 x 128 tile)       2 attn_bwd_kernel (tile, bf16 / bf16x3 operands)
+ *             3 attn_bwd2_kernel (tile, exact fp32)    4 xq_fwd / xq_bwd_kernel (one lane per query, keys in LDS)
+ *             5 xq2_fwd / xq2_bwd_kernel (one lane per query, key tile in registers)
+ *   direction 0 forward, 1 backward
+ *   targ      the kernel's template argument: head width D = 32 | 24 | 16 (4), NW = 4 (5), 0 for the tile families
+ *   precision the operand mode of the kernel that runs: 0 exact fp32, 1 bf16, 3 bf16x3 (families 3, 4, 5: always 0)
+ *   norm      1 with the q/k LayerNorm, 0 without
+ *   threads   per block: 256 (1, 2, 3, 5), 128 (4)
+ *   lds_bytes dynamic LDS of the launch: 53 760 (1), 72 192 (2, 3), 0 (4, 5)
+ *   tail      launches that follow a backward kernel: bit 0 attn_extra_fixup_kernel (borrowed rows with a side buffer),
+ *             bit 1 attn_ln_reduce_kernel (the norm's parameter gradients); forward: 0 */
+int lotus_attention_last_route(int* out);
 
 /* ---- composite entry points (csrc/blocks.cpp): ONE call enqueues the whole forward / backward of a sub-block by chaining
  * the entry points above in the order the per-launch host path uses (bit-identical results).  The caller passes three flat

@@ -1,5 +1,4 @@
-// lotus-hip: tile attention forward/backward in exact fp32 (MFMA 32x32x2) — one kernel pair
-// serves both attention sites of the reference:
+// lotus-hip: attention forward / backward for the two attention sites of the reference:
 //   * SerializedAttention (PointTransformerV3/model.py:468-557, flash var-len path): patches of
 //     <= 128 serialised points; q/k/v rows are gathered from qkv[N][3C] through order[pad]; the
 //     result is scattered back through the owner positions (unpad[inverse]).
@@ -9,18 +8,33 @@
 // the softmax core in fp16 (model.py:544); here it is fp32 end-to-end, which is what the 1e-4
 // logit parity against the fp32-ideal oracle requires (SURVEY.md Trap 2).
 //
-// LDS plan (floats): row images Q[128][33] K[128][33] V[128][33] (+ dO[128][33] in backward) — 51 / 68 KB.  There is NO
+// Five kernel families; attn_route() at the end of the file chooses between them, and the choice of the last call can be read
+// back (attn_route.h):
+//   1 attn_fwd_kernel<PREC, NORM>   128 x 128 tile forward (fp32 MFMA 32x32x2, or bf16 / bf16x3 operands).  The patch attention
+//                                   in every mode; the cross attention when its key side is long or unknown; NORM = false:
+//                                   every call without q/k LayerNorm.
+//   2 attn_bwd_kernel<1 | 3>        tile backward on bf16 / bf16x3 operands: the same call sites as 1 in those modes.
+//   3 attn_bwd2_kernel<NORM>        tile backward in exact fp32: the same call sites as 1 at precision 0.
+//   4 xq_fwd / xq_bwd_kernel<D>     one lane per query, keys as LDS broadcast rows, D = 32 | 24 | 16: the cross attention
+//                                   (<= 32 keys) at head widths 24 / 16, with owner flags, with borrowed rows or under
+//                                   LOTUS_XQ=3; the patch attention under LOTUS_XQ=2.
+//   5 xq2_fwd / xq2_bwd_kernel<4>   one lane per query, the key tile in registers: the cross attention proper (head width 32,
+//                                   <= 32 keys, plain rows) — what the model's cross attention runs by default.
+// attn_ln_reduce_kernel (the q/k LayerNorm parameter gradients) and attn_extra_fixup_kernel (borrowed tail-patch rows) follow a
+// backward kernel of any family.
+//
+// LDS plan of the tile kernels (floats): row images Q[128][33] K[128][33] V[128][33] (+ dO[128][33] in backward) — 51 / 68 KB.  There is NO
 // score image: scores are computed transposed (S^T = K Q^T) so that a lane owns one query and its accumulator registers
 // run over the keys; softmax, dropout and the P / dS operands of the following products live in registers (see the
 // comments at the kernels).  Everything a (tile, head) needs stays on chip between the QK^T, softmax and PV stages.
 #include "mma.h"
+#include "attn_route.h"
 #include <stdlib.h>
 
 namespace LOTUS_NS {
 
 #define AT 128        // tile rows (queries) and max keys
 #define ALD 33        // row stride of the [128][d<=32] images
-#define SLD 129       // row stride of the score image
 
 struct AttnP {
   const act_t* q; long q_ld; int q_off;
@@ -68,22 +82,10 @@ __device__ __forceinline__ f32x16 zero16() {
   return z;
 }
 
-// Load `len` rows (gathered through idx) of d floats at column offset coff into img[128][ALD];
-// rows >= len and columns >= d are zero.  8 threads per row, float4 each.
-__device__ __forceinline__ void load_rows(float* img, const act_t* base, long ld, int coff, const int* rows_s,
-                                          int len, int d) {
-  const int sub = threadIdx.x & 7;
-  for (int r = threadIdx.x >> 3; r < AT; r += 32) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < len && sub * 4 < d) v = ld4(base + (long)rows_s[r] * ld + coff + sub * 4);
-    float* o = img + r * ALD + sub * 4;
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-  }
-}
-
-// The same for N images at once with ALL global loads issued before the first LDS store: load_rows called N times
-// runs N x 4 load -> s_waitcnt -> store round trips back to back (measured: ~13 serialised HBM latencies = most of a
-// forward block's 23 us); here they are 4 N independent loads in flight.
+// Load, for N images at once, `len` rows (gathered through rows_s) of d floats at column offset coff into img[128][ALD]; rows
+// >= len and columns >= d are zero.  8 threads per row, float4 each.  ALL global loads are issued before the first LDS store:
+// one image after the other ran N x 4 load -> s_waitcnt -> store round trips back to back (measured: ~13 serialised HBM
+// latencies = most of a forward block's 23 us); here they are 4 N independent loads in flight.
 struct RowSrc {
   float* img;
   const act_t* base;
@@ -140,7 +142,7 @@ __device__ __forceinline__ void ln_rows(float* img, float* rstd_s, int row, int 
 }
 
 struct AttnSmem {
-  float* Q; float* K; float* V; float* dO; float* S;
+  float* Q; float* K; float* V; float* dO;
   float* qrstd; float* krstd; float* Dv; float* lse;
   float* gq; float* bq; float* gk; float* bk;
   int* qrow; int* krow; int* qown; int* kext;
@@ -153,7 +155,6 @@ __device__ __forceinline__ AttnSmem carve(float* base, bool bwd) {
   s.K = p; p += AT * ALD;
   s.V = p; p += AT * ALD;
   s.dO = p; if (bwd) p += AT * ALD;
-  s.S = nullptr;  // scores live in registers (transposed-accumulator formulation)
   s.qrstd = p; p += AT;
   s.krstd = p; p += AT;
   s.Dv = p; if (bwd) p += AT;   // (backward only: the forward block must stay under 160 KB / 3)
@@ -414,8 +415,10 @@ __device__ __forceinline__ void ln_rows_bwd(float* g, const float* xh, const flo
   for (int j = 0; j < d; ++j) gr[j] = rs * (gr[j] * gam[j] - s1 - xr[j] * s2);
 }
 
+// Tile backward on bf16 (PREC 1) / bf16x3 (PREC 3) operands; exact fp32 is attn_bwd2_kernel.
 template <int PREC>
 __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnP p) {
+  static_assert(PREC == 1 || PREC == 3, "bf16 / bf16x3 operands only: the exact-fp32 backward is attn_bwd2_kernel");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   AttnSmem s = carve(smem, true);
   __shared__ float lnacc[4][32];
@@ -503,32 +506,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnP p) {
       const int kj = rk + l31;
       // q_norm's affine is folded into the hoisted key fragment: (xq g + b) . kn = xq . (g kn) + b . kn, so the
       // A operand is the raw normalised row and the bias term is one per-key constant
-      float kb[16], vb[16], c_a = 0.f;
-      uint4 kbh[2], kbl[2], vbh[2], vbl[2];  // bf16 paths: the same fragments as whole MFMA operands (k = 16 q2 + 8 hh + j)
-      if constexpr (PREC != 0) {
+      float c_a = 0.f;
+      uint4 kbh[2], kbl[2], vbh[2], vbl[2];  // the hoisted fragments as whole MFMA operands (k = 16 q2 + 8 hh + j)
 #pragma unroll
-        for (int q2 = 0; q2 < 2; ++q2) {
-          float k8[8], v8[8];
+      for (int q2 = 0; q2 < 2; ++q2) {
+        float k8[8], v8[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int k = 16 * q2 + 8 * hh + j;
-            const float kn = s.K[kj * ALD + k] * s.gk[k] + s.bk[k];
-            c_a += s.bq[k] * kn;
-            k8[j] = kn * s.gq[k];
-            v8[j] = s.V[kj * ALD + k];
-          }
-          split8<PREC>(k8, kbh[q2], kbl[q2]);
-          split8<PREC>(v8, vbh[q2], vbl[q2]);
-        }
-      } else {
-#pragma unroll
-        for (int s2 = 0; s2 < 16; ++s2) {
-          const int k = 2 * s2 + hh;
+        for (int j = 0; j < 8; ++j) {
+          const int k = 16 * q2 + 8 * hh + j;
           const float kn = s.K[kj * ALD + k] * s.gk[k] + s.bk[k];
           c_a += s.bq[k] * kn;
-          kb[s2] = kn * s.gq[k];
-          vb[s2] = s.V[kj * ALD + k];
+          k8[j] = kn * s.gq[k];
+          v8[j] = s.V[kj * ALD + k];
         }
+        split8<PREC>(k8, kbh[q2], kbl[q2]);
+        split8<PREC>(v8, vbh[q2], vbl[q2]);
       }
       c_a += __shfl_xor(c_a, 32, 64);
       // dropout index ((tile * H + h) * 128 + q) * 128 + key: the tile/head part is a multiple of 2^14, so the
@@ -539,30 +531,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnP p) {
       const int qtiles = (q_len + 31) / 32;
       for (int qt = share_k ? wave : 0; qt < qtiles; qt += share_k ? 4 : 1) {
         f32x16 sa = zero16(), dpa = zero16();
-        const float* qrow_p = s.Q + (qt * 32 + l31) * ALD + hh;
-        const float* dorow_p = s.dO + (qt * 32 + l31) * ALD + hh;
-        if constexpr (PREC != 0) {
+        const int qoff = (qt * 32 + l31) * ALD;  // this lane's row of the Q / dO images
 #pragma unroll
-          for (int q2 = 0; q2 < 2; ++q2) {
-            if (q2 * 16 >= d) continue;
-            float q8[8], d8[8];
+        for (int q2 = 0; q2 < 2; ++q2) {
+          if (q2 * 16 >= d) continue;
+          float q8[8], d8[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              q8[j] = s.Q[(qt * 32 + l31) * ALD + 16 * q2 + 8 * hh + j];
-              d8[j] = s.dO[(qt * 32 + l31) * ALD + 16 * q2 + 8 * hh + j];
-            }
-            uint4 ah, al, bh, bl;
-            split8<PREC>(q8, ah, al);
-            split8<PREC>(d8, bh, bl);
-            sa = mfma_split<PREC>(ah, al, kbh[q2], kbl[q2], sa);
-            dpa = mfma_split<PREC>(bh, bl, vbh[q2], vbl[q2], dpa);
+          for (int j = 0; j < 8; ++j) {
+            q8[j] = s.Q[qoff + 16 * q2 + 8 * hh + j];
+            d8[j] = s.dO[qoff + 16 * q2 + 8 * hh + j];
           }
-        } else {
-#pragma unroll
-          for (int s2 = 0; s2 < 16; ++s2) {
-            sa = __builtin_amdgcn_mfma_f32_32x32x2f32(qrow_p[2 * s2], kb[s2], sa, 0, 0, 0);
-            dpa = __builtin_amdgcn_mfma_f32_32x32x2f32(dorow_p[2 * s2], vb[s2], dpa, 0, 0, 0);
-          }
+          uint4 ah, al, bh, bl;
+          split8<PREC>(q8, ah, al);
+          split8<PREC>(d8, bh, bl);
+          sa = mfma_split<PREC>(ah, al, kbh[q2], kbl[q2], sa);
+          dpa = mfma_split<PREC>(bh, bl, vbh[q2], vbl[q2], dpa);
         }
         float lse4[16], d4[16];  // per-query scalars of this lane's 16 rows: four aligned runs of four queries
 #pragma unroll
@@ -582,34 +565,25 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnP p) {
           sa[r] = keep ? pv * p.drop_inv_keep : 0.f;                                                   // dropout(P)
           dpa[r] = p.scale * pv * ((keep ? dpa[r] * p.drop_inv_keep : 0.f) - d4[r]);                   // dS
         }
-        if constexpr (PREC != 0) {
-          // registers 8g .. 8g+7 are this lane's k-slots of MFMA g: queries 16g + (j & 3) + 8 (j >> 2) + 4 hh
+        // registers 8g .. 8g+7 are this lane's k-slots of MFMA g: queries 16g + (j & 3) + 8 (j >> 2) + 4 hh
 #pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            float p8[8], s8[8], o8[8], q8[8];
+        for (int g = 0; g < 2; ++g) {
+          float p8[8], s8[8], o8[8], q8[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const int qq = qt * 32 + 16 * g + (j & 3) + 8 * (j >> 2) + 4 * hh;
-              p8[j] = sa[8 * g + j];
-              s8[j] = dpa[8 * g + j];
-              o8[j] = s.dO[qq * ALD + l31];
-              q8[j] = s.Q[qq * ALD + l31] * gq_l + bq_l;
-            }
-            uint4 ph, pl, sh, sl, oh, ol, qh, ql;
-            split8<PREC>(p8, ph, pl);
-            split8<PREC>(s8, sh, sl);
-            split8<PREC>(o8, oh, ol);
-            split8<PREC>(q8, qh, ql);
-            acc_dv = mfma_split<PREC>(oh, ol, ph, pl, acc_dv);
-            acc_dk = mfma_split<PREC>(qh, ql, sh, sl, acc_dk);
+          for (int j = 0; j < 8; ++j) {
+            const int qq = qt * 32 + 16 * g + (j & 3) + 8 * (j >> 2) + 4 * hh;
+            p8[j] = sa[8 * g + j];
+            s8[j] = dpa[8 * g + j];
+            o8[j] = s.dO[qq * ALD + l31];
+            q8[j] = s.Q[qq * ALD + l31] * gq_l + bq_l;
           }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int qq = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            acc_dv = __builtin_amdgcn_mfma_f32_32x32x2f32(s.dO[qq * ALD + l31], sa[r], acc_dv, 0, 0, 0);
-            acc_dk = __builtin_amdgcn_mfma_f32_32x32x2f32(s.Q[qq * ALD + l31] * gq_l + bq_l, dpa[r], acc_dk, 0, 0, 0);
-          }
+          uint4 ph, pl, sh, sl, oh, ol, qh, ql;
+          split8<PREC>(p8, ph, pl);
+          split8<PREC>(s8, sh, sl);
+          split8<PREC>(o8, oh, ol);
+          split8<PREC>(q8, qh, ql);
+          acc_dv = mfma_split<PREC>(oh, ol, ph, pl, acc_dv);
+          acc_dk = mfma_split<PREC>(qh, ql, sh, sl, acc_dk);
         }
       }
     }
@@ -618,32 +592,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnP p) {
     f32x16 acc_dq = zero16();
     if (r0 < q_len) {
       const int qi = r0 + l31;
-      float qb[16], dob[16], c_b = 0.f;  // k_norm's affine folded into the hoisted query fragment (as above)
+      float c_b = 0.f;  // k_norm's affine folded into the hoisted query fragment (as above)
       uint4 qbh[2], qbl[2], dobh[2], dobl[2];
-      if constexpr (PREC != 0) {
 #pragma unroll
-        for (int q2 = 0; q2 < 2; ++q2) {
-          float q8[8], d8[8];
+      for (int q2 = 0; q2 < 2; ++q2) {
+        float q8[8], d8[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int k = 16 * q2 + 8 * hh + j;
-            const float qn = s.Q[qi * ALD + k] * s.gq[k] + s.bq[k];
-            c_b += s.bk[k] * qn;
-            q8[j] = qn * s.gk[k];
-            d8[j] = s.dO[qi * ALD + k];
-          }
-          split8<PREC>(q8, qbh[q2], qbl[q2]);
-          split8<PREC>(d8, dobh[q2], dobl[q2]);
-        }
-      } else {
-#pragma unroll
-        for (int s2 = 0; s2 < 16; ++s2) {
-          const int k = 2 * s2 + hh;
+        for (int j = 0; j < 8; ++j) {
+          const int k = 16 * q2 + 8 * hh + j;
           const float qn = s.Q[qi * ALD + k] * s.gq[k] + s.bq[k];
           c_b += s.bk[k] * qn;
-          qb[s2] = qn * s.gk[k];
-          dob[s2] = s.dO[qi * ALD + k];
+          q8[j] = qn * s.gk[k];
+          d8[j] = s.dO[qi * ALD + k];
         }
+        split8<PREC>(q8, qbh[q2], qbl[q2]);
+        split8<PREC>(d8, dobh[q2], dobl[q2]);
       }
       c_b += __shfl_xor(c_b, 32, 64);
       const float lse_q = s.lse[qi], d_q = s.Dv[qi];
@@ -652,30 +615,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnP p) {
       const unsigned c2 = (unsigned)(tb >> 32) * 0x7FEB352Du + (unsigned)(p.drop_seed >> 32);
       for (int t = 0; t < ktiles; ++t) {
         f32x16 sb = zero16(), dpb = zero16();
-        const float* krow_p = s.K + (t * 32 + l31) * ALD + hh;
-        const float* vrow_p = s.V + (t * 32 + l31) * ALD + hh;
-        if constexpr (PREC != 0) {
+        const int koff = (t * 32 + l31) * ALD;  // this lane's row of the K / V images
 #pragma unroll
-          for (int q2 = 0; q2 < 2; ++q2) {
-            if (q2 * 16 >= d) continue;
-            float k8[8], v8[8];
+        for (int q2 = 0; q2 < 2; ++q2) {
+          if (q2 * 16 >= d) continue;
+          float k8[8], v8[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              k8[j] = s.K[(t * 32 + l31) * ALD + 16 * q2 + 8 * hh + j];
-              v8[j] = s.V[(t * 32 + l31) * ALD + 16 * q2 + 8 * hh + j];
-            }
-            uint4 ah, al, bh, bl;
-            split8<PREC>(k8, ah, al);
-            split8<PREC>(v8, bh, bl);
-            sb = mfma_split<PREC>(ah, al, qbh[q2], qbl[q2], sb);
-            dpb = mfma_split<PREC>(bh, bl, dobh[q2], dobl[q2], dpb);
+          for (int j = 0; j < 8; ++j) {
+            k8[j] = s.K[koff + 16 * q2 + 8 * hh + j];
+            v8[j] = s.V[koff + 16 * q2 + 8 * hh + j];
           }
-        } else {
-#pragma unroll
-          for (int s2 = 0; s2 < 16; ++s2) {
-            sb = __builtin_amdgcn_mfma_f32_32x32x2f32(krow_p[2 * s2], qb[s2], sb, 0, 0, 0);
-            dpb = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow_p[2 * s2], dob[s2], dpb, 0, 0, 0);
-          }
+          uint4 ah, al, bh, bl;
+          split8<PREC>(k8, ah, al);
+          split8<PREC>(v8, bh, bl);
+          sb = mfma_split<PREC>(ah, al, qbh[q2], qbl[q2], sb);
+          dpb = mfma_split<PREC>(bh, bl, dobh[q2], dobl[q2], dpb);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -685,27 +639,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnP p) {
           const bool keep = !p.drop_thresh || keep_lo(lo_b + key, s0, c2, p.drop_thresh);
           sb[r] = p.scale * pv * ((keep ? dpb[r] * p.drop_inv_keep : 0.f) - d_q);                      // dS^T
         }
-        if constexpr (PREC != 0) {
 #pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            float s8[8], k8[8];
+        for (int g = 0; g < 2; ++g) {
+          float s8[8], k8[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const int key = t * 32 + 16 * g + (j & 3) + 8 * (j >> 2) + 4 * hh;
-              s8[j] = sb[8 * g + j];
-              k8[j] = s.K[key * ALD + l31] * gk_l + bk_l;
-            }
-            uint4 sh, sl, kh, kl;
-            split8<PREC>(s8, sh, sl);
-            split8<PREC>(k8, kh, kl);
-            acc_dq = mfma_split<PREC>(kh, kl, sh, sl, acc_dq);
+          for (int j = 0; j < 8; ++j) {
+            const int key = t * 32 + 16 * g + (j & 3) + 8 * (j >> 2) + 4 * hh;
+            s8[j] = sb[8 * g + j];
+            k8[j] = s.K[key * ALD + l31] * gk_l + bk_l;
           }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            acc_dq = __builtin_amdgcn_mfma_f32_32x32x2f32(s.K[key * ALD + l31] * gk_l + bk_l, sb[r], acc_dq, 0, 0, 0);
-          }
+          uint4 sh, sl, kh, kl;
+          split8<PREC>(s8, sh, sl);
+          split8<PREC>(k8, kh, kl);
+          acc_dq = mfma_split<PREC>(kh, kl, sh, sl, acc_dq);
         }
       }
     }
@@ -808,9 +754,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnP p) {
   if (tid < 128) p.ln_part[((long)(blockIdx.x * p.H + h) * 4 + (tid >> 5)) * 32 + (tid & 31)] = lnacc[tid >> 5][tid & 31];
 }
 
-// ---- exact-fp32 backward, second formulation (round 5).  On gfx950 an fp32 MFMA and a vector-ALU instruction never overlap
-// on a SIMD (tools/ubench/mfma_coissue.hip), so a block's time is MFMA cycles PLUS ~5 cycles per other vector instruction;
-// attn_bwd_kernel<0> spent 11 vector instructions per MFMA and recomputed S / dP in a second orientation for dQ.  Here:
+// ---- exact-fp32 backward: the only one (attn_bwd_kernel above exists for bf16 / bf16x3 operands alone).  On gfx950 an fp32
+// MFMA and a vector-ALU instruction never overlap on a SIMD (tools/ubench/mfma_coissue.hip), so a block's time is MFMA cycles
+// PLUS ~5 cycles per other vector instruction.  The two-orientation formulation of attn_bwd_kernel, which recomputes S / dP a
+// second time for dQ, costs 11 vector instructions per MFMA when its products are fp32; this kernel is built around fewer:
 //   * S, P and dS exist ONCE, in the orientation lane <-> key (dV, dK reduce over the queries a lane's registers run over);
 //   * dQ reduces over the keys, which sit on lanes: every wave drops its dS tile (32 keys x 32 queries) into an LDS exchange
 //     image X[key][query] (aliased onto the V image: V lives in hoisted registers by then; 16-byte chunks XOR-swizzled so that
@@ -820,7 +767,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnP p) {
 //   * the softmax scale, log2(e) and the q_norm bias term are folded into the hoisted key fragment and into the accumulator's
 //     INITIAL value (P = exp2(acc - lse2[q]): two instructions), row / key bounds ride on +-inf instead of selects, and the
 //     dropout hash advances by compile-time constants (one multiply per element instead of two).
-// Per query tile and wave: 96 + 16 MFMA-equivalents and ~300 vector instructions (was 144 and ~750).
+// Per query tile and wave: 96 + 16 MFMA-equivalents and ~300 vector instructions (the two-orientation form on fp32 products:
+// 144 and ~750).
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int xswz(int key) { return ((key & 1) << 2) | ((key >> 1) & 3); }
@@ -1959,10 +1907,76 @@ static int xq_mode() {
   if (on < 0) { const char* e = getenv("LOTUS_XQ"); on = e ? atoi(e) : 1; }
   return on;
 }
-static bool xq_ok(int k_max, int precision, int atomic_out, int d) {
-  const bool geom = !atomic_out && (d == 32 || d == 24 || d == 16);
+
+// ---- the dispatch: which kernel a call runs and how it is launched.  Both entry points ask attn_route, note its answer
+// (attn_route.h) and launch from it (attn_launch).
+struct AttnRoute {
+  int family;     // LOTUS_ATTN_*
+  int targ;       // the kernel's template argument: D (xq), NW (xq2), 0 for the tile families
+  int precision;  // operand mode of the kernel that runs (the query-per-lane kernels: always 0)
+  int threads;
+  size_t lds;     // dynamic LDS bytes of the launch
+  int tail;       // LOTUS_ATTN_TAIL_*: the launches that follow a backward kernel
+};
+// bwd: direction; norm: norm_mode(); owner / extra: the call has owner flags / borrowed rows with a side buffer (p.dkv_extra;
+// backward only); atomic_out: backward only; xq: xq_mode().  The build flavour is LOTUS_ACT_IS_BF16.
+static AttnRoute attn_route(bool bwd, int norm, int precision, int d, int k_max, bool owner, bool extra, int atomic_out, int xq) {
+  const int tail = !bwd ? 0 : (extra ? LOTUS_ATTN_TAIL_FIXUP : 0) | (norm ? LOTUS_ATTN_TAIL_LN_REDUCE : 0);
   const bool short_keys = k_max > 0 && k_max <= 32;
-  return geom && ((short_keys && xq_mode() >= 1) || (!short_keys && precision == 0 && !LOTUS_ACT_IS_BF16 && xq_mode() == 2));
+  // the query-per-lane kernels have no variant without the norm
+  const bool per_lane = norm && !atomic_out && (d == 32 || d == 24 || d == 16) &&
+                        ((short_keys && xq >= 1) || (!short_keys && precision == 0 && !LOTUS_ACT_IS_BF16 && xq == 2));
+  if (per_lane) {
+    // the cross attention proper (head width 32, <= 32 keys, plain rows): key tile in registers, queries streamed
+    if (d == 32 && short_keys && !owner && !extra && xq != 3) return {LOTUS_ATTN_XQ2, 4, 0, 256, 0, tail};
+    return {LOTUS_ATTN_XQ, d, 0, 128, 0, tail};
+  }
+  const int prec = (precision == 3 || precision == 1) ? precision : 0;  // (without the norm only 0 gets this far)
+  if (!bwd) return {LOTUS_ATTN_FWD, 0, prec, 256, attn_smem_bytes(false), tail};
+  return {prec ? LOTUS_ATTN_BWD : LOTUS_ATTN_BWD2, 0, prec, 256, attn_smem_bytes(true), tail};
+}
+static void attn_note(const AttnRoute& r, bool bwd, int norm) {
+  lotus_note_attn_route(r.family, bwd, r.targ, r.precision, norm, r.threads, (int)r.lds, r.tail);
+}
+
+// The main kernel of a route over n tiles (forward) / blocks (backward).  Every kernel is named here once, as the token
+// LOTUS_LAUNCH sees.
+static void attn_launch(const AttnRoute& r, bool bwd, int norm, int n, const AttnP& p, hipStream_t st) {
+  const dim3 grid(n, p.H), block(r.threads);
+#define ATTN_TILE(kernel) do { lotus_allow_dyn_lds_once<kernel>(r.lds); LOTUS_LAUNCH(kernel, grid, block, r.lds, st, p); } while (0)
+#define ATTN_LANE(kernel) LOTUS_LAUNCH(kernel, grid, block, 0, st, p)
+  switch (r.family) {
+    case LOTUS_ATTN_FWD:
+      if (!norm) ATTN_TILE((attn_fwd_kernel<0, false>));
+      else if (r.precision == 3) ATTN_TILE(attn_fwd_kernel<3>);
+      else if (r.precision == 1) ATTN_TILE(attn_fwd_kernel<1>);
+      else ATTN_TILE(attn_fwd_kernel<0>);
+      break;
+    case LOTUS_ATTN_BWD:
+      if (r.precision == 3) ATTN_TILE(attn_bwd_kernel<3>);
+      else ATTN_TILE(attn_bwd_kernel<1>);
+      break;
+    case LOTUS_ATTN_BWD2:
+      if (norm) ATTN_TILE(attn_bwd2_kernel<true>);
+      else ATTN_TILE(attn_bwd2_kernel<false>);
+      break;
+    case LOTUS_ATTN_XQ:
+      if (!bwd) {
+        if (r.targ == 32) ATTN_LANE(xq_fwd_kernel<32>);
+        else if (r.targ == 24) ATTN_LANE(xq_fwd_kernel<24>);
+        else ATTN_LANE(xq_fwd_kernel<16>);
+      } else {
+        if (r.targ == 32) ATTN_LANE(xq_bwd_kernel<32>);
+        else if (r.targ == 24) ATTN_LANE(xq_bwd_kernel<24>);
+        else ATTN_LANE(xq_bwd_kernel<16>);
+      }
+      break;
+    default:
+      if (!bwd) ATTN_LANE(xq2_fwd_kernel<4>);
+      else ATTN_LANE(xq2_bwd_kernel<4>);
+  }
+#undef ATTN_TILE
+#undef ATTN_LANE
 }
 
 static int check_geom(int H, int d) { return (d % 4 == 0 && d <= 32 && d >= 4 && H > 0) ? 0 : -1; }
@@ -2003,35 +2017,9 @@ int lotus_attention_fwd(const act_t* q, long q_ld, int q_off, const act_t* kv, l
   p.qn_w = qn_w; p.qn_b = qn_b; p.kn_w = kn_w; p.kn_b = kn_b;
   p.out = out; p.out_ld = out_ld; p.lse = lse; p.H = H; p.d = d; p.scale = scale; p.eps = eps;
   set_attn_drop(p, drop_p, drop_seed);
-  if (!norm) {  // always the tile kernel: the query-per-lane kernels have no variant without the norm
-    const size_t sm = attn_smem_bytes(false);
-    const auto attn_fwd_plain = attn_fwd_kernel<0, false>;  // (one token for the launch macro)
-    { static bool a0 = false; if (!a0) { (void)hipFuncSetAttribute((const void*)attn_fwd_plain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a0 = true; } }
-    LOTUS_LAUNCH(attn_fwd_plain, dim3(ntiles, H), dim3(256), sm, (hipStream_t)stream, p);
-    LOTUS_LAUNCH_CHECK("lotus_attention_fwd(no q/k norm)");
-    return LOTUS_OK;
-  }
-  if (xq_ok(k_max, precision, 0, d)) {  // one lane per query, keys as LDS broadcast rows
-    if (d == 32 && k_max > 0 && k_max <= 32 && !owner && xq_mode() != 3)  // the cross attention proper: key tile in registers
-      LOTUS_LAUNCH(xq2_fwd_kernel<4>, dim3(ntiles, H), dim3(256), 0, (hipStream_t)stream, p);
-    else if (d == 32) LOTUS_LAUNCH(xq_fwd_kernel<32>, dim3(ntiles, H), dim3(128), 0, (hipStream_t)stream, p);
-    else if (d == 24) LOTUS_LAUNCH(xq_fwd_kernel<24>, dim3(ntiles, H), dim3(128), 0, (hipStream_t)stream, p);
-    else LOTUS_LAUNCH(xq_fwd_kernel<16>, dim3(ntiles, H), dim3(128), 0, (hipStream_t)stream, p);
-    LOTUS_LAUNCH_CHECK("lotus_attention_fwd(query per lane)");
-    return LOTUS_OK;
-  }
-  const size_t sm = attn_smem_bytes(false);
-  const int prec = precision;
-  if (prec == 3) {
-    { static bool a1 = false; if (!a1) { (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a1 = true; } }
-    LOTUS_LAUNCH(attn_fwd_kernel<3>, dim3(ntiles, H), dim3(256), sm, (hipStream_t)stream, p);
-  } else if (prec == 1) {
-    { static bool a2 = false; if (!a2) { (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a2 = true; } }
-    LOTUS_LAUNCH(attn_fwd_kernel<1>, dim3(ntiles, H), dim3(256), sm, (hipStream_t)stream, p);
-  } else {
-    { static bool a3 = false; if (!a3) { (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a3 = true; } }
-    LOTUS_LAUNCH(attn_fwd_kernel<0>, dim3(ntiles, H), dim3(256), sm, (hipStream_t)stream, p);
-  }
+  const AttnRoute r = attn_route(false, norm, precision, d, k_max, owner != nullptr, false, 0, xq_mode());
+  attn_note(r, false, norm);
+  attn_launch(r, false, norm, ntiles, p, (hipStream_t)stream);
   LOTUS_LAUNCH_CHECK("lotus_attention_fwd");
   return LOTUS_OK;
 }
@@ -2039,8 +2027,8 @@ int lotus_attention_fwd(const act_t* q, long q_ld, int q_off, const act_t* kv, l
 size_t lotus_attention_bwd_workspace(int nblocks, int H) { return (size_t)nblocks * H * 4 * 32 * sizeof(float); }
 
 // Backward.  blocks: int32 [nblocks][6] = first_tile, n_tiles, tile_step, part_slot, k_start, k_len.
-// dq/dkv must be zero-initialised by the caller when atomic_out = 1.  With atomic_out = 0 every
-// (part_slot, key row, head) is written exactly once (plain stores, deterministic).
+// dq/dkv must be zero-initialised by the caller when atomic_out = 1 (fp32 storage only: the bf16 twin refuses it).  With
+// atomic_out = 0 every (part_slot, key row, head) is written exactly once (plain stores, deterministic).
 int lotus_attention_bwd(const act_t* q, long q_ld, int q_off, const act_t* kv, long kv_ld, int k_off, int v_off,
                         const int* qidx, const int* kidx, const int* owner, const int* tiles, const int* blocks,
                         int nblocks, const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b,
@@ -2054,6 +2042,8 @@ int lotus_attention_bwd(const act_t* q, long q_ld, int q_off, const act_t* kv, l
   const int norm = norm_mode(qn_w, qn_b, kn_w, kn_b);
   LOTUS_CHECK_ARG(norm >= 0, "lotus_attention_bwd: bad arguments (qn_w, qn_b, kn_w, kn_b must be all given or all null)");
   if (!norm) LOTUS_CHECK_NO_NORM("lotus_attention_bwd", precision);
+  LOTUS_CHECK_ARG(!(LOTUS_ACT_IS_BF16 && atomic_out), "lotus_attention_bwd: atomic_out = %d is not built for bf16 activation "
+                  "storage (store_rows has no bf16 atomic add: the gradients would be stored, not accumulated)", atomic_out);
   LOTUS_CHECK_ARG(!norm || (dqn_w && dqn_b && dkn_w && dkn_b), "lotus_attention_bwd: bad arguments (null norm gradient)");
   LOTUS_CHECK_ARG(!norm || (workspace && workspace_bytes >= lotus_attention_bwd_workspace(nblocks, H)),
                   "lotus_attention_bwd: workspace too small");
@@ -2073,49 +2063,32 @@ int lotus_attention_bwd(const act_t* q, long q_ld, int q_off, const act_t* kv, l
   p.H = H; p.d = d; p.scale = scale; p.eps = eps;
   set_attn_drop(p, drop_p, drop_seed);
   hipStream_t st = (hipStream_t)stream;
-  const size_t sm = attn_smem_bytes(true);
-  const int prec = precision;
+  const AttnRoute r = attn_route(true, norm, precision, d, k_max, owner != nullptr, p.dkv_extra != nullptr, atomic_out, xq_mode());
+  attn_note(r, true, norm);
+  // main kernel, then the borrowed rows' fix-up, then the reduction of the norm partials; the stop event rides on the last
+  const bool fixup = r.tail & LOTUS_ATTN_TAIL_FIXUP, ln_reduce = r.tail & LOTUS_ATTN_TAIL_LN_REDUCE;
   StopEventOnLast stop_ev;
-  if (!norm) {
-    // always the tile kernel (no query-per-lane variant); no norm partials, so no reduction: it or the fix-up is the last launch
-    { static bool a7 = false; if (!a7) { (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a7 = true; } }
-    if (!p.dkv_extra) stop_ev.last();
-    LOTUS_LAUNCH(attn_bwd2_kernel<false>, dim3(nblocks, H), dim3(256), sm, st, p);
-    if (p.dkv_extra) {
-      const int w4 = 2 * H * d / 4;
-      stop_ev.last();
-      LOTUS_LAUNCH(attn_extra_fixup_kernel, dim3(cdiv((long)n_extra * w4, 256)), dim3(256), 0, st, dkv_extra, 2L * H * d,
-                         ext_pos, kidx, n_extra, w4, dkv, dkv_ld, dk_off);
-    }
-    LOTUS_LAUNCH_CHECK("lotus_attention_bwd(no q/k norm)");
-    return LOTUS_OK;
-  }
-  if (xq_ok(k_max, precision, atomic_out, d)) {
-    // the cross attention proper (head width 32, <= 32 keys, plain rows): keys in registers, queries streamed (xq2_bwd_kernel)
-    if (d == 32 && k_max > 0 && k_max <= 32 && !owner && !p.dkv_extra && xq_mode() != 3)
-      LOTUS_LAUNCH(xq2_bwd_kernel<4>, dim3(nblocks, H), dim3(256), 0, st, p);
-    else if (d == 32) LOTUS_LAUNCH(xq_bwd_kernel<32>, dim3(nblocks, H), dim3(128), 0, st, p);
-    else if (d == 24) LOTUS_LAUNCH(xq_bwd_kernel<24>, dim3(nblocks, H), dim3(128), 0, st, p);
-    else LOTUS_LAUNCH(xq_bwd_kernel<16>, dim3(nblocks, H), dim3(128), 0, st, p);
-  } else if (prec == 3) {
-    { static bool a4 = false; if (!a4) { (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a4 = true; } }
-    LOTUS_LAUNCH(attn_bwd_kernel<3>, dim3(nblocks, H), dim3(256), sm, st, p);
-  } else if (prec == 1) {
-    { static bool a5 = false; if (!a5) { (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a5 = true; } }
-    LOTUS_LAUNCH(attn_bwd_kernel<1>, dim3(nblocks, H), dim3(256), sm, st, p);
-  } else {
-    { static bool a6 = false; if (!a6) { (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); a6 = true; } }
-    LOTUS_LAUNCH(attn_bwd2_kernel<true>, dim3(nblocks, H), dim3(256), sm, st, p);
-  }
-  if (p.dkv_extra) {
+  if (!fixup && !ln_reduce) stop_ev.last();
+  attn_launch(r, true, norm, nblocks, p, st);
+  if (fixup) {
     const int w4 = 2 * H * d / 4;
+    if (!ln_reduce) stop_ev.last();
     LOTUS_LAUNCH(attn_extra_fixup_kernel, dim3(cdiv((long)n_extra * w4, 256)), dim3(256), 0, st, dkv_extra, 2L * H * d,
                        ext_pos, kidx, n_extra, w4, dkv, dkv_ld, dk_off);
   }
-  stop_ev.last();
-  LOTUS_LAUNCH(attn_ln_reduce_kernel, dim3(4), dim3(1024), 0, st, p.ln_part, dqn_w, dqn_b, dkn_w, dkn_b,
-                     nblocks * H, d, accumulate);
+  if (ln_reduce) {
+    stop_ev.last();
+    LOTUS_LAUNCH(attn_ln_reduce_kernel, dim3(4), dim3(1024), 0, st, p.ln_part, dqn_w, dqn_b, dkn_w, dkn_b,
+                       nblocks * H, d, accumulate);
+  }
   LOTUS_LAUNCH_CHECK("lotus_attention_bwd");
+  return LOTUS_OK;
+}
+
+// diagnostic: the kernel the calling thread's last attention launch was given to (attn_route.h; fields in lotus_hip.h)
+int lotus_attention_last_route(int* out) {
+  LOTUS_CHECK_ARG(out, "lotus_attention_last_route: out is null");
+  for (int i = 0; i < 8; ++i) out[i] = lotus_tls_attn_route[i];
   return LOTUS_OK;
 }
 

@@ -34,6 +34,18 @@ static inline int lotus_exp_skip(const char* name) {
     else                                                                                                                 \
       hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                                 \
   } while (0)
+// A kernel whose dynamic LDS exceeds the 64 KB default limit is allowed its size once per process, before its first launch
+// (the call takes a lock in the runtime: never per launch).  Keyed on the kernel's VALUE, so every kernel — each instantiation
+// of a template too — owns its flag; a helper keyed on the kernel's type would share one between all void(P) kernels.  The
+// first size a kernel is given stands, as it did when every call site carried its own flag.
+template <auto Kernel>
+static inline void lotus_allow_dyn_lds_once(size_t bytes) {
+  static bool done = false;
+  if (!done) {
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    done = true;
+  }
+}
 // An entry point with several launches hands an armed stop event to its LAST launch only (a completion event costs the
 // launching queue ~4 us per kernel that carries it): hold it on entry, call last() right before the final launch.
 struct StopEventOnLast {

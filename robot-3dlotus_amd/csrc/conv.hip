@@ -805,19 +805,19 @@ int lotus_subm_conv(int mode, const act_t* x, const float* w, const float* w_t, 
   if (p.ND <= 64) {
     dim3 grid(cdiv(p.ND, 64), cdiv(n, 128));
     if (mode == 0) {
-      { static bool a1 = false; if (!a1) { (void)hipFuncSetAttribute((const void*)conv_kernel<128, 64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); a1 = true; } }
+      lotus_allow_dyn_lds_once<conv_kernel<128, 64, true>>(dyn);
       LOTUS_LAUNCH((conv_kernel<128, 64, true>), grid, block, dyn, st, p);
     } else {
-      { static bool a2 = false; if (!a2) { (void)hipFuncSetAttribute((const void*)conv_kernel<128, 64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); a2 = true; } }
+      lotus_allow_dyn_lds_once<conv_kernel<128, 64, false>>(dyn);
       LOTUS_LAUNCH((conv_kernel<128, 64, false>), grid, block, dyn, st, p);
     }
   } else {
     dim3 grid(cdiv(p.ND, 128), cdiv(n, 128));
     if (mode == 0) {
-      { static bool a3 = false; if (!a3) { (void)hipFuncSetAttribute((const void*)conv_kernel<128, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); a3 = true; } }
+      lotus_allow_dyn_lds_once<conv_kernel<128, 128, true>>(dyn);
       LOTUS_LAUNCH((conv_kernel<128, 128, true>), grid, block, dyn, st, p);
     } else {
-      { static bool a4 = false; if (!a4) { (void)hipFuncSetAttribute((const void*)conv_kernel<128, 128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); a4 = true; } }
+      lotus_allow_dyn_lds_once<conv_kernel<128, 128, false>>(dyn);
       LOTUS_LAUNCH((conv_kernel<128, 128, false>), grid, block, dyn, st, p);
     }
   }

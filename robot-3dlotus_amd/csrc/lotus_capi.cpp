@@ -14,6 +14,9 @@ __attribute__((visibility("hidden"))) __thread int lotus_tls_dense_route[8] = {0
 // route of the calling thread's last sparse-convolution launch (conv_route.h; read by lotus_conv_last_route)
 __attribute__((visibility("hidden"))) __thread int lotus_tls_conv_route[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
+// route of the calling thread's last attention launch (attn_route.h; read by lotus_attention_last_route)
+__attribute__((visibility("hidden"))) __thread int lotus_tls_attn_route[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
 void lotus_set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);

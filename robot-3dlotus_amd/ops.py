@@ -59,6 +59,21 @@ def last_conv_route():
     return ConvRoute(*out)
 
 
+AttnRoute = collections.namedtuple("AttnRoute", "family direction targ precision norm threads lds_bytes tail")
+ATTN_FWD, ATTN_BWD, ATTN_BWD2, ATTN_XQ, ATTN_XQ2 = range(1, 6)
+
+
+def last_attn_route():
+    """The kernel this thread's last attention launch was given to (lotus_attention_last_route; fields in include/lotus_hip.h):
+    family 1 tile forward, 2 tile backward on bf16 / bf16x3 operands, 3 tile backward in fp32, 4 / 5 one lane per query (keys in
+    LDS / in registers); direction 0 fwd / 1 bwd; template argument; operand precision; with the q/k norm; threads; dynamic LDS
+    bytes; tail (bit 0 fix-up, bit 1 norm-gradient reduction follow).  Set when the kernel is chosen, so it is there after a
+    launch that failed, too."""
+    out = (ctypes.c_int * 8)()
+    _capi.call_raw("lotus_attention_last_route", ctypes.addressof(out))
+    return AttnRoute(*out)
+
+
 class _Timed:
     """Bracket a dense launch with HIP events on the stream it is enqueued on (diagnostic; only when EVENT_LOG is set)."""
 

@@ -130,17 +130,21 @@ def _patch_inputs(C, H, n, seed):
     return qkv, qn, kn, dout
 
 
-def _patch_run(ops, lv, qc, qnc, knc, doutc, C, H, dtype=torch.float32, drop=0.0, seed=0):
-    """Forward and backward into guarded buffers; -> dict name -> (buffer, view), and the four norm gradients."""
+def _patch_run(ops, lv, qc, qnc, knc, doutc, C, H, dtype=torch.float32, drop=0.0, seed=0, routes=None):
+    """Forward and backward into guarded buffers; -> dict name -> (buffer, view), and the four norm gradients.  `routes` (a
+    list) receives the route record after the forward and after the backward call (ops.last_attn_route)."""
     n, d = lv.n, C // H
     b = dict(att=_guarded(n, C, dtype), lse=_guarded(lv.npad, H), dqkv=_guarded(n, 3 * C, dtype),
              extra=_guarded(max(lv.n_extra, 1), 2 * C, dtype))
     att, lse, dqkv, extra = (b[k][1] for k in ("att", "lse", "dqkv", "extra"))
     ops.attention_fwd(qc, 3 * C, 0, qc, 3 * C, C, 2 * C, lv.gidx, lv.gidx, lv.owner, lv.self_tiles, lv.n_self_tiles,
                       qnc, knc, att, lse, H, d, drop, seed)
+    fwd_route = ops.last_attn_route()
     gr = ops.attention_bwd(qc, 3 * C, 0, qc, 3 * C, C, 2 * C, lv.gidx, lv.gidx, lv.owner, lv.self_tiles, lv.self_blocks,
                            lv.n_self_tiles, qnc, knc, att, doutc, lse, dqkv, 3 * C, 0, dqkv, 3 * C, C, 2 * C, 0, 0, H, d, drop, seed,
                            lv.kext, lv.ext_pos, lv.n_extra, extra)
+    if routes is not None:
+        routes += [fwd_route, ops.last_attn_route()]
     return b, gr
 
 
@@ -167,8 +171,16 @@ def test_patch_attention_edges_fwd_bwd(C, H, slot):
     pr = [t.double().requires_grad_(True) for t in (*qn, *kn)]
     oref = om.patch_attention(qd, _oracle_level(r), slot, H, pr[0], pr[1], pr[2], pr[3], 128)
     oref.backward(dout.double())
-    b, gr = _patch_run(ops, lv, qkv.cuda(), tuple(t.cuda() for t in qn), tuple(t.cuda() for t in kn), dout.cuda(), C, H)
+    routes = []
+    b, gr = _patch_run(ops, lv, qkv.cuda(), tuple(t.cuda() for t in qn), tuple(t.cuda() for t in kn), dout.cuda(), C, H, routes=routes)
     _guards_intact(**b)
+    # the kernels this case means: the exact-fp32 tile pair, or under LOTUS_XQ=2 the query-per-lane pair of this head width;
+    # the edge patches borrow rows, so the fix-up follows the backward kernel, and the norm-gradient reduction always does
+    assert lv.n_extra > 0
+    R = ops.AttnRoute
+    want = ([R(4, 0, C // H, 0, 1, 128, 0, 0), R(4, 1, C // H, 0, 1, 128, 0, 3)] if XQ == "2" else
+            [R(1, 0, 0, 0, 1, 256, 53760, 0), R(3, 1, 0, 0, 1, 256, 72192, 3)])
+    assert routes == want, (routes, want)
     rec, fails = {}, []
     fails.append(_per_cloud(rec, "fwd", b["att"][1], oref, counts, 5e-6))
     fails.append(_per_cloud(rec, "dqkv", b["dqkv"][1], qd.grad, counts, 2e-5))
@@ -199,10 +211,14 @@ def test_patch_attention_edges_bf16_storage():
     qd = qkv.double().requires_grad_(True)
     oref = om.patch_attention(qd, _oracle_level(r), 0, H, qn[0].double(), qn[1].double(), kn[0].double(), kn[1].double(), 128)
     oref.backward(dout.double())
+    routes = []
     with ops.storage(BF):
         b, gr = _patch_run(ops, lv, qkv.cuda().to(BF), tuple(t.cuda() for t in qn), tuple(t.cuda() for t in kn),
-                           dout.cuda().to(BF), C, H, dtype=BF)
+                           dout.cuda().to(BF), C, H, dtype=BF, routes=routes)
     _guards_intact(**b)
+    R = ops.AttnRoute  # (read through the twin's record function inside the storage block: the record is one)
+    assert routes == [R(1, 0, 0, 1, 1, 256, 53760, 0), R(2, 1, 0, 1, 1, 256, 72192, 3)], routes
+    assert ops.last_attn_route() == routes[1], "the fp32 entry point reads the record the twin wrote"
     rec, fails = {}, []
     fails.append(_per_cloud(rec, "fwd", b["att"][1], oref, counts, 1.5e-2))
     fails.append(_per_cloud(rec, "dqkv", b["dqkv"][1], qd.grad, counts, 3e-2))
@@ -277,12 +293,14 @@ def _cross_setup(layout, C, H):
     return lv, counts, txt, q, kv, qn, kn, dout
 
 
-def _cross_run(ops, lv, qc, kvc, qnc, knc, doutc, C, H, L, k_max, drop=0.0, backward=True):
+def _cross_run(ops, lv, qc, kvc, qnc, knc, doutc, C, H, L, k_max, drop=0.0, backward=True, routes=None):
     n, d, G = lv.n, C // H, lv.ca_groups
+    routes = [] if routes is None else routes
     b = dict(att=_guarded(n, C), lse=_guarded(n, H))
     att, lse = b["att"][1], b["lse"][1]
     ops.attention_fwd(qc, C, 0, kvc, 2 * C, 0, C, None, None, None, lv.ca_tiles, lv.n_ca_tiles, qnc, knc, att, lse, H, d,
                       drop_p=drop, seed=77, k_max=k_max)
+    routes.append(ops.last_attn_route())
     gr = None
     if backward:
         b.update(dq=_guarded(n, C), dkvp=_guarded(G * L * 2 * C))
@@ -290,6 +308,7 @@ def _cross_run(ops, lv, qc, kvc, qnc, knc, doutc, C, H, L, k_max, drop=0.0, back
         gr = ops.attention_bwd(qc, C, 0, kvc, 2 * C, 0, C, None, None, None, lv.ca_tiles, lv.ca_blocks, lv.n_ca_blocks, qnc,
                                knc, att, doutc, lse, b["dq"][1], C, 0, dkvp, 2 * C, 0, C, L * 2 * C, 0, H, d, drop_p=drop, seed=77,
                                k_max=k_max)
+        routes.append(ops.last_attn_route())
     _guards_intact(**b)
     return b, gr
 
@@ -320,8 +339,19 @@ def test_cross_attention_edges_fwd_bwd(layout, path, C, H):
     lv, counts, txt, q, kv, qn, kn, dout = _cross_setup(layout, C, H)
     L = sum(txt)
     k_max = _k_max(lv, layout, path)
+    routes = []
     b, gr = _cross_run(ops, lv, q.cuda(), kv.cuda(), tuple(t.cuda() for t in qn), tuple(t.cuda() for t in kn), dout.cuda(),
-                       C, H, L, k_max)
+                       C, H, L, k_max, routes=routes)
+    # the kernels this path means.  short_keys: the key-tile-in-registers pair at head width 32 (the round-5 pair under
+    # LOTUS_XQ=3), the keys-in-LDS pair at head width 24; tile (k_max = 0) and dispatch (k_max = 78): the exact-fp32 tile pair
+    R, d = ops.AttnRoute, C // H
+    if path != "short_keys":
+        want = [R(1, 0, 0, 0, 1, 256, 53760, 0), R(3, 1, 0, 0, 1, 256, 72192, 2)]
+    elif d == 32 and XQ != "3":
+        want = [R(5, 0, 4, 0, 1, 256, 0, 0), R(5, 1, 4, 0, 1, 256, 0, 2)]
+    else:
+        want = [R(4, 0, d, 0, 1, 128, 0, 0), R(4, 1, d, 0, 1, 128, 0, 2)]
+    assert routes == want, (routes, want)
     qd, kvd = q.double().requires_grad_(True), kv.double().requires_grad_(True)
     pr = [t.double().requires_grad_(True) for t in (*qn, *kn)]
     oref = om.cross_attention(qd, kvd, counts, txt, H, pr[0], pr[1], pr[2], pr[3])

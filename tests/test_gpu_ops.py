@@ -432,6 +432,18 @@ def test_subm_conv_bf16_operands_pair_compacted_path():
 
 
 # ------------------------------------------------------------------------------------ attention
+def _attn_routes_are(ops, got, lane, tail):
+    """got = the records after a forward and a backward call with the q/k norm in exact fp32; lane = None: the tile pair
+    (attn_fwd_kernel<0>, attn_bwd2_kernel<true>), else (family, template argument) of the query-per-lane pair."""
+    R = ops.AttnRoute
+    if lane is None:
+        want = [R(1, 0, 0, 0, 1, 256, 53760, 0), R(3, 1, 0, 0, 1, 256, 72192, tail)]
+    else:
+        threads = 128 if lane[0] == 4 else 256
+        want = [R(lane[0], 0, lane[1], 0, 1, threads, 0, 0), R(lane[0], 1, lane[1], 0, 1, threads, 0, tail)]
+    assert got == want, (got, want)
+
+
 @pytest.mark.parametrize("C,H", [(64, 2), (128, 4), (768, 32)])
 def test_patch_attention_fwd_bwd(C, H):
     ops = _ops()
@@ -456,12 +468,17 @@ def test_patch_attention_fwd_bwd(C, H):
     lse = torch.empty(lv.npad, H, device="cuda")
     ops.attention_fwd(qc, 3 * C, 0, qc, 3 * C, C, 2 * C, lv.gidx, lv.gidx, lv.owner, lv.self_tiles, lv.n_self_tiles,
                       qnc, knc, att, lse, H, d)
+    routes = [ops.last_attn_route()]
     _close(att, oref, 5e-6, "attn fwd")
     dqkv = torch.empty(n, 3 * C, device="cuda")
     extra = torch.empty(max(lv.n_extra, 1), 2 * C, device="cuda")
     gr = ops.attention_bwd(qc, 3 * C, 0, qc, 3 * C, C, 2 * C, lv.gidx, lv.gidx, lv.owner, lv.self_tiles, lv.self_blocks,
                            lv.n_self_tiles, qnc, knc, att, dev(dout), lse, dqkv, 3 * C, 0, dqkv, 3 * C, C, 2 * C, 0, 0, H, d, 0.0, 0,
                            lv.kext, lv.ext_pos, lv.n_extra, extra)
+    # the tile pair; in the LOTUS_XQ=2 child (test_patch_attention_query_per_lane_path) the keys-in-LDS pair of this head width
+    import os
+    routes.append(ops.last_attn_route())
+    _attn_routes_are(ops, routes, (4, d) if os.environ.get("LOTUS_XQ") == "2" else None, tail=3 if lv.n_extra else 2)
     _close(dqkv, qd.grad, 2e-5, "attn dqkv")
     for name, a, b in zip(("dqn_w", "dqn_b", "dkn_w", "dkn_b"), gr, pr):
         # dkn_b is mathematically zero (softmax is shift-invariant per query): pure fp32 cancellation noise
@@ -579,7 +596,18 @@ def test_cross_attention_fwd_bwd(C, H, drop, path):
         return dq, dkvp.sum(0), gr
 
     att, lse = run(k_max)
+    routes = [ops.last_attn_route()]
     dq, dkv, gr = back(k_max, att, lse)
+    routes.append(ops.last_attn_route())
+    # the pair each path means, by LOTUS_XQ (unset here; "2" and "3" in the children of the two tests above)
+    import os
+    xq = os.environ.get("LOTUS_XQ") or "1"
+    assert xq in ("1", "2", "3")
+    if path == "short_keys":    # key tile in registers at head width 32 (not under "3"), keys in LDS at 24
+        lane = (5, 4) if (d == 32 and xq != "3") else (4, d)
+    else:                       # k_max = 0: the tile pair, unless "2" moves every exact-fp32 call to the keys-in-LDS pair
+        lane = (4, d) if xq == "2" else None
+    _attn_routes_are(ops, routes, lane, tail=2)
     if drop == 0.0:
         qd, kvd = q.double().requires_grad_(True), kv.double().requires_grad_(True)
         pr = [t.double().requires_grad_(True) for t in (*qn, *kn)]

@@ -51,9 +51,15 @@ def _plain_run(C, H, slot):
     pc, counts, txt, ref, got = ge._levels("patch", "", 1)
     r, lv = ref[0], got[0].for_order(slot)
     qkv, dout = pu.plain_inputs(C, lv.n, seed=1000 + C + H + slot)
-    b, gr = ge._patch_run(ops, lv, qkv.cuda(), None, None, dout.cuda(), C, H)
+    routes = []
+    b, gr = ge._patch_run(ops, lv, qkv.cuda(), None, None, dout.cuda(), C, H, routes=routes)
     ge._guards_intact(**b)
     assert gr == [None] * 4
+    # the NORM = false tile pair whatever LOTUS_XQ says (this runs in the LOTUS_XQ=2 child too): norm 0, no norm-gradient
+    # reduction (tail bit 1 clear); the fix-up of the borrowed rows is the only launch after the backward kernel
+    assert lv.n_extra > 0
+    R = ops.AttnRoute
+    assert routes == [R(1, 0, 0, 0, 0, 256, 53760, 0), R(3, 1, 0, 0, 0, 256, 72192, 1)], routes
     return b, lv, r, counts, qkv, dout
 
 
