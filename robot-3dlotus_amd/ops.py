@@ -109,8 +109,13 @@ class _Timed:
 # several nodes further down the dgrad chain.  Valid when nothing reads a parameter gradient during
 # backward — i.e. `.grad is None` on entry (zero_grad(set_to_none=True): autograd adopts the tensor without
 # touching it) and no per-parameter hooks; the GradReducer (hooks) and gradient accumulation need the
-# default "node".  Tensors the side stream reads are held until that join (_hold_for_side) so the caching allocator does
-# not hand their memory to the main stream early.
+# default "node".
+#
+# In BOTH modes the tensors the side stream reads are held until the join that orders the main stream behind it, so the
+# caching allocator (which knows of no use on another stream) cannot hand their memory to the main stream early: "node" keeps
+# them in the node's own list (_NODE_HELD, dropped by `_joined` right behind its join — a body such as ffn_branch_bwd frees its
+# temporaries when it returns, and the node goes on allocating after that), "end" in _HELD until the end-of-backward join
+# (_hold_for_side).
 SIDE = None
 _SIDE_ON = os.environ.get("LOTUS_SIDE_STREAM", "1") != "0"
 _STEM_WGRAD_MAIN = True  # the last weight gradient of a backward pass runs on the critical stream, idle by then (+0.45 %)
@@ -279,7 +284,7 @@ def _side_ws(nbytes, dev):
 class _OnSide:
     """Run a weight-gradient producer on a side stream after the main stream's pending work.  Outputs are
     allocated by the caller on the main stream (they stay alive until after the join); `reads` are the tensors
-    the side-stream kernels consume.  Inside the block every ops.call() enqueues on the side stream
+    the side-stream kernels consume, kept alive from here until the join.  Inside the block every ops.call() enqueues on the side stream
     (_capi.STREAM_OVERRIDE); torch's current stream is left alone — nothing in these blocks launches ATen kernels —
     and the fork is one event record + stream wait through the C-ABI stream link."""
 
@@ -295,8 +300,11 @@ class _OnSide:
         _RR = (_RR + 1) % _NSIDE
         side, ptr = _SIDES[_CUR]
         _capi.call_raw("lotus_streamlink_wait", _LINK, _capi.stream_ptr(), ptr)
-        if _JOIN == "end":  # no join at the end of the node: the memory must not go back to the main stream early
+        # until the join the memory must not go back to the main stream, whatever the caller does with its own references
+        if _JOIN == "end":
             _hold_for_side(self.reads, side)
+        elif _NODE_HELD is not None:
+            _NODE_HELD.append(self.reads)
         _capi.STREAM_OVERRIDE = ptr
         return self
 
@@ -306,6 +314,9 @@ class _OnSide:
 
 
 _HELD = []  # tensors the weight-gradient stream reads, kept alive until the end-of-backward join (deferred-join mode)
+# "node" mode: the `reads` of every fork of the `_joined` node being run, dropped behind its join; None outside such a node
+# (the weight packing in forward forks too: it reads parameters only, and its caller joins)
+_NODE_HELD = None
 
 
 def _hold_for_side(reads, side):
@@ -352,12 +363,14 @@ def _fwd(fn):
 
 def _joined(fn):
     """backward() decorator: join the side stream before the gradients leave the node ("node"), or once at the
-    end of the backward pass ("end"); the node's products run in the precision its forward captured."""
+    end of the backward pass ("end"); the node's products run in the precision its forward captured.  "node": what the node's
+    forks read (_NODE_HELD) is released behind the join, also when the node raises."""
     def wrapped(ctx, *grads):
-        global _IN_NODE, _END_CB_PENDING, _PREC
+        global _IN_NODE, _END_CB_PENDING, _PREC, _NODE_HELD
         _IN_NODE += 1
         prev, _PREC = _PREC, getattr(ctx, "prec", _PREC)
         prev_bf, _capi.BF16 = _capi.BF16, getattr(ctx, "bf", _capi.BF16)
+        outer, _NODE_HELD = _NODE_HELD, ([] if _JOIN == "node" else None)
         try:
             if _JOIN == "end" and _SIDE_ON and not _END_CB_PENDING:
                 _END_CB_PENDING = True
@@ -367,8 +380,11 @@ def _joined(fn):
             _PREC = prev
             _capi.BF16 = prev_bf
             _IN_NODE -= 1
-            if _JOIN == "node":
-                sync_side_stream()
+            try:
+                if _JOIN == "node":
+                    sync_side_stream()
+            finally:
+                _NODE_HELD = outer  # (freed behind the join: whatever re-uses the memory is enqueued after it)
     return staticmethod(wrapped)
 
 
@@ -1206,8 +1222,8 @@ def _bwd_buffers(n_grads, n_tmp, ws_main, ws_side, dev, reads, rows):
 
 
 def _side_ctx(dev, ws_side_bytes, reads, rows=0):
-    """(side stream pointer or 0, its workspace, its counters) for a composite backward; in the deferred-join mode the
-    tensors the side stream reads are announced to the allocator (as _OnSide does)."""
+    """(side stream pointer or 0, its workspace, its counters) for a composite backward; the tensors the side stream reads
+    are held until the join (as _OnSide does; in the "node" mode they are locals of the node's backward() as well)."""
     global _CUR
     if _side() is None:  # (measured and not kept: the big levels' weight gradients on the critical stream, 907 / 883 / 861 vs 930)
         return 0, None, None
@@ -1215,6 +1231,8 @@ def _side_ctx(dev, ws_side_bytes, reads, rows=0):
     st, ptr = _SIDES[0]
     if _JOIN == "end":
         _hold_for_side(reads, st)
+    elif _NODE_HELD is not None:
+        _NODE_HELD.append(reads)
     ws = _side_ws(ws_side_bytes, dev)
     return ptr, ws, _counters_for(dev, ptr)
 
