@@ -594,34 +594,60 @@ static inline int vec_ok(const void* p, long ld) { return (((uintptr_t)p) % 16 =
 
 #define GEMM_KALIGN 64  // split-K ranges are multiples of the largest slab depth
 
-// Element types of a launch: A is always an activation; B is the weight matrix (fp32 master) except in the weight gradient
-// (both operands are activations); C is an activation except for the weight gradient and for split-K partial slabs
-// (p.c_float).  In the fp32 build every combination is <float, float, float>.
-#define GEMM_GO_RD(BM_, BN_, BK_, PREC_, grid_, RD_)                                                                             \
-  do {                                                                                                                           \
-    using TB_ = std::conditional_t<SUM_A, act_t, float>;                                                                         \
-    /* (the route record sits beside each launch: a combination that launches nothing records nothing) */                        \
-    auto note_ = [&] { lotus_note_dense_route(1, BM_, BN_, BK_, nz, FAST, FAST && p.cnt && nz > 1, RD_); };                      \
-    if constexpr (LOTUS_ACT_IS_BF16 && !SUM_A) {                                                                                 \
-      if (p.b_act) { /* bf16 weight shadow: half the weight bytes per block, no conversion while staging */                      \
-        if constexpr (PREC_ == 1 && FAST) {                                                                                      \
-          note_();                                                                                                               \
-          if (p.c_float) LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, act_t, float, RD_>), grid_, block, 0, st, p); \
-          else LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, act_t, act_t, RD_>), grid_, block, 0, st, p); \
-        }                                                                                                                        \
-      } else if (p.c_float) {                                                                                                    \
-        note_();                                                                                                                 \
-        LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, TB_, float, RD_>), grid_, block, 0, st, p); \
-      } else {                                                                                                                   \
-        note_();                                                                                                                 \
-        LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, TB_, act_t, RD_>), grid_, block, 0, st, p); \
-      }                                                                                                                          \
-    } else {                                                                                                                     \
-      note_();                                                                                                                   \
-      LOTUS_LAUNCH((gemm_kernel<BM_, BN_, BK_, A_KC, B_KC, SUM_A, FAST, PREC_, act_t, TB_, float, RD_>), grid_, block, 0, st, p);      \
-    }                                                                                                                            \
-  } while (0)
-#define GEMM_GO(BM_, BN_, BK_, PREC_, grid_) GEMM_GO_RD(BM_, BN_, BK_, PREC_, grid_, 1)
+static inline bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
+
+// FAST needs float4-safe extents on both operands: the contiguous dimension must be a multiple of 4 (K for k-contiguous
+// operands, M / N otherwise) and at least 4 wide; the output and every tensor of the epilogue 16-byte aligned
+static bool gemm_fast_ok(const GemmP& p, int layout) {
+  const bool a_kc = layout != GEMM_WGRAD, b_kc = layout == GEMM_FWD;
+  const bool a_ok = p.a_vec && (a_kc ? (p.K % 4 == 0 && p.K >= 4) : (p.M % 4 == 0 && p.M >= 4));
+  const bool b_ok = p.b_vec && (b_kc ? (p.K % 4 == 0 && p.K >= 4) : (p.N % 4 == 0 && p.N >= 4));
+  const bool c_ok = p.N % 4 == 0 && p.ldc % 4 == 0 && p.part_stride % 4 == 0 && vec_ok(p.C, p.ldc) && al16(p.bias) &&
+                    al16(p.residual) && al16(p.pre) && al16(p.mulpre) && al16(p.part);
+  return a_ok && b_ok && c_ok;
+}
+
+// The switches of the LDS-DMA kernels (include/lotus_hip.h), read once per process
+struct GemmDmaEnv {
+  int on;            // LOTUS_GEMM_DMA: 0 = off
+  // LOTUS_GEMM_DMA_MINROWS: smallest row count (forward / input gradient: rows of the activation operand; weight gradient:
+  // length of the reduction) these kernels are used from.  Measured (tools/lab/gemm_lab, MI355X): they win from ~16 k rows;
+  // below that the grids are too small for 128-row tiles and gemm_kernel's deep-slab / split-K forms are the better fit.
+  int minrows;
+  // LOTUS_GEMM_DMA_MINBLOCKS: 128-row tiles need a grid that fills the GPU: measured in the step (bench.py --gemm-report), the
+  // level-1 products (23 894 rows) with <= 128 output columns — 187 blocks — lose 10-20 % to gemm_kernel's 64 x 64 tiles, the
+  // 512-wide ones win
+  int minblocks;
+  int wgrad_blocks;  // LOTUS_GEMM_DMA_WGRAD_BLOCKS: 0 = weight gradients stay on gemm_kernel
+};
+static const GemmDmaEnv& gemm_dma_env() {
+  static const GemmDmaEnv env = [] {
+    auto get = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    return GemmDmaEnv{get("LOTUS_GEMM_DMA", 1), get("LOTUS_GEMM_DMA_MINROWS", 16384), get("LOTUS_GEMM_DMA_MINBLOCKS", 400),
+                      get("LOTUS_GEMM_DMA_WGRAD_BLOCKS", 256)};
+  }();
+  return env;
+}
+
+// Split count of a weight gradient dW[N, K] over M activation rows when it runs on the LDS-DMA kernels (0: it does not).  Known
+// from the shape alone (the workspace query has no pointers): ~1 block per CU on 128 x 128 (64-wide where a side is 64) output
+// tiles, at least 256 rows per split, a multiple of 8 (one XCD / L2 per split, see the kernel's block order).
+static int gemm_dma_wgrad_splits(int M, int N, int K, const GemmDmaEnv& env) {
+  if (LOTUS_ACT_IS_BF16 || !env.on || env.wgrad_blocks <= 0 || M < env.minrows || (N & 3) || (K & 3)) return 0;
+  const long tiles = (long)cdiv(N, N > 64 ? 128 : 64) * cdiv(K, K > 64 ? 128 : 64);
+  long nz = (env.wgrad_blocks + tiles - 1) / tiles;
+  nz = nz >= 8 ? (nz / 8) * 8 : nz;
+  if (nz < 1) nz = 1;
+  // Measured (tools/dbg/dma_onoff.py): with fewer than ~256 rows per split a block is a cold prologue and a handful of
+  // slabs — 23 894 x 128 x 128 (one 128 x 128 tile): 33 us here against 20.8 us on gemm_kernel's 64 x 64 tiles — those stay there
+  return M / nz >= 256 ? (int)nz : 0;
+}
+
+// what the LDS-DMA descriptors need of the three matrices: 16-byte aligned rows, extents below the limits of a buffer descriptor
+static bool dma_operands_ok(const GemmP& p, long a_rows, long b_rows, long a_max, long c_max) {
+  return al16(p.A) && al16(p.B) && al16(p.C) && !((p.lda | p.ldb | p.ldc | p.N) & 3) && a_rows * p.lda * 4 < a_max &&
+         b_rows * p.ldb * 4 < (1L << 32) && (long)p.M * p.ldc * 4 < c_max;
+}
 
 // Tuning constants of gemm_kernel.  Every one of them was an environment switch while it was being measured (rounds 1-4;
 // DESIGN.md section 4 has the A/B of each); the losers and their code are gone, these are the values that shipped:
@@ -635,111 +661,161 @@ static inline int vec_ok(const void* p, long ld) { return (((uintptr_t)p) % 16 =
 constexpr long kF32RingMaxBlocks = 8192;
 constexpr int kBf16RingMaxRows = 8192;
 
-template <bool A_KC, bool B_KC, bool SUM_A, bool FAST>
-static int launch_gemm_t(GemmP& p, int nz, hipStream_t st) {
-  const long blocks64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64);
-  dim3 block(256);
-  dim3 g64(cdiv(p.N, 64), cdiv(p.M, 64), nz);
-  const int g_prec = p.prec;
-  if (g_prec && SUM_A && FAST && !A_KC && !B_KC) {
-    // weight gradients (split-K, 64x64 tiles): operands converted while staged; bias sums from the fp32 registers
-    if constexpr (SUM_A && !A_KC && !B_KC && FAST) {
-      if (g_prec == 1) {
-        if constexpr (LOTUS_ACT_IS_BF16) {
-          if (p.K <= kBf16RingMaxRows) GEMM_GO_RD(64, 64, 32, 1, g64, 4);
-          else GEMM_GO(64, 64, 32, 1, g64);
-        } else {
-          GEMM_GO(64, 64, 32, 1, g64);
-        }
-      } else if constexpr (!LOTUS_ACT_IS_BF16) GEMM_GO(64, 64, 32, 3, g64);
+// THE decision of the dense layers: the kernel, tile and launch shape of the prepared product `p` in `layout`, split into nz
+// ranges — or the refusal.  Pure: no launch, no record, no environment (env = gemm_dma_env()).  The LDS-DMA kernels first where
+// they apply, else gemm_kernel.  It returns no gemm_kernel / gemm_dma_kernel form that gemm_launch / gemm_dma_launch do not name.
+static GemmRoute gemm_route(const GemmP& p, int layout, int nz, const GemmDmaEnv& env) {
+  constexpr bool bf16 = LOTUS_ACT_IS_BF16;
+  const bool wgrad = layout == GEMM_WGRAD, fast = gemm_fast_ok(p, layout), wide = p.N > 64;
+  GemmRoute r = {};
+  r.layout = layout; r.nz = nz; r.fast = 1; r.tap = p.tap_rows != 0;
+  r.fused = p.cnt && nz > 1;
+  const bool dma = !bf16 && env.on && p.prec == 0 && !p.b_act;  // the LDS-DMA kernels: exact fp32 products, fp32 storage
+  if (dma && r.tap) {
+    // the tap-grouped sparse convolution on the LDS-DMA tiles (p as lotus_conv_tap_gemm sets it up; the launch takes the
+    // reduction in one range, klen = K).  The grid covers the worst case — every row of every tap active; the host does not
+    // know the pair counts — and its blocks past the last active tile leave after the scan of the 27 counters.
+    r.family = 3; r.bm = 128; r.bn = wide ? 128 : 64; r.bk = wide ? 16 : 32; r.depth = wide ? 3 : 2;
+    r.grid = dim3(cdiv(p.N, r.bn), 27 * cdiv(p.tap_rows, 128));
+    r.name = "lotus_subm_conv(tap-grouped, dma)";
+    if (!wgrad && p.a_rows && p.tap_cnt && p.tap_rows > 0 && !(p.tap_rows & 63) && p.a_src_rows > 0 && !(p.b_tap_stride & 3) &&
+        p.K % r.bk == 0 && dma_operands_ok(p, p.a_src_rows, p.K > p.N ? p.K : p.N, 0x7ffffff0L, 1L << 31) && !p.bias && !p.residual &&
+        !p.pre && !p.mulpre && p.act == LOTUS_ACT_NONE && !p.drop_thresh)
+      return r;
+  } else if (dma && fast) {  // (FAST: the epilogue's tensors are 16-byte aligned)
+    // tall products on gemm_dma_kernel: 128-row tiles, 128 x 128 x 16 on three LDS stages (measured and removed: four stages =
+    // 64 KB = two blocks per CU, to leave LDS for the other queue's blocks: 941 / 944 / 944 against 944 / 946 / 947 samples/s
+    // with three) above 64 output columns; a weight gradient dW[p.M, p.N] of <= 64 rows on 64-row tiles
+    const bool ln = p.ln_x != nullptr, tall = !wgrad || p.M > 64;
+    r.family = 2; r.bm = tall ? 128 : 64; r.bn = wide ? 128 : 64; r.bk = tall && wide ? 16 : 32; r.depth = tall == wide ? 3 : 2;
+    r.epi = ln ? 2 : (p.act != LOTUS_ACT_NONE || p.mulpre || p.drop_thresh) ? 1 : 0;
+    r.grid = dim3(cdiv(p.N, r.bn), cdiv(p.M, r.bm), nz);
+    r.name = "lotus_gemm(dma)";
+    bool ok = (wgrad ? p.K : p.M) >= env.minrows && (!p.accumulate || r.fused) &&
+              dma_operands_ok(p, wgrad ? p.K : p.M, layout == GEMM_FWD ? p.N : p.K, 1L << 32, 1L << 32);
+    if (wgrad) {
+      // its own split plan (another count: the plan of gemm_kernel); no epilogue (lotus_linear_wgrad asks for none)
+      ok = ok && gemm_dma_wgrad_splits(p.K, p.M, p.N, env) == nz && !(p.M & 3) && (nz == 1 || p.klen % 32 == 0) && r.epi == 0;
+    } else {
+      // a k-contiguous operand is staged in whole slabs: the reduction (and every split of it) must be a multiple of the slab
+      // depth.  (With the LayerNorm backward in the epilogue a whole kernel and four HBM passes go away: worth it on any grid
+      // that covers half the CUs.)
+      ok = ok && (long)r.grid.x * r.grid.y * nz >= (ln ? 128 : env.minblocks) && p.K % r.bk == 0 && (nz == 1 || p.klen % r.bk == 0);
     }
-    LOTUS_LAUNCH_CHECK("lotus_gemm(bf16 wgrad)");
-    return LOTUS_OK;
+    // the LayerNorm backward: an input gradient whose tile covers whole rows, nothing else in the epilogue
+    if (ln) ok = ok && layout == GEMM_DGRAD && nz == 1 && (p.N == 64 || p.N == 128) && p.ldc == p.N && p.act == LOTUS_ACT_NONE &&
+                 !p.mulpre && !p.pre && !p.bias && al16(p.ln_x) && al16(p.ln_gamma) && al16(p.ln_dz) && p.ln_part && p.ln_mean && p.ln_rstd;
+    if (ok) return r;
   }
-  if (p.b_act && !(LOTUS_ACT_IS_BF16 && g_prec == 1 && !SUM_A && FAST && (A_KC || p.M % 4 == 0))) {
-    lotus_set_error("lotus_linear: bf16 weight shadows (precision 5) need the bf16-storage build and 16-byte aligned operands whose "
-                    "widths are multiples of 4");
-    return LOTUS_E_UNSUPPORTED;
-  }
-  if (g_prec && !SUM_A && FAST && (A_KC || p.M % 4 == 0)) {
-    // bf16 / bf16x3 operand path (forward and input-gradient products).  bf16 storage: one bf16 MFMA covers 16 k, so a
-    // 32-deep slab is two MFMAs per wave between barriers and the block pays one global-load round trip per slab; the
-    // staging ring keeps four slabs in flight where the grid is small enough to afford its registers.
-    if constexpr (!SUM_A && FAST) {
-      if (g_prec == 1) {
-        if constexpr (LOTUS_ACT_IS_BF16) {
-          if (p.M <= kBf16RingMaxRows) GEMM_GO_RD(64, 64, 32, 1, g64, 4);
-          else GEMM_GO(64, 64, 32, 1, g64);
-        } else GEMM_GO(64, 64, 32, 1, g64);
-      } else if constexpr (!LOTUS_ACT_IS_BF16) {
-        GEMM_GO(64, 64, 32, 3, g64);
-      }
-    }
-    LOTUS_LAUNCH_CHECK("lotus_gemm(bf16)");
-    return LOTUS_OK;
-  }
-  if constexpr (LOTUS_ACT_IS_BF16) {
-    // bf16-storage build: the exact-fp32 product path only serves the shapes the vectorised bf16 path cannot take
-    // (odd widths such as the 90- and 217-wide head layers)
-    GEMM_GO(64, 64, 32, 0, g64);
+  if (p.ln_x) return GemmRoute{LOTUS_GEMM_NA, nullptr};  // (gemm_kernel has no LayerNorm epilogue: the caller runs two launches)
+  if (r.tap && (bf16 || wgrad || !fast))
+    return GemmRoute{LOTUS_E_UNSUPPORTED, "lotus_subm_conv(tap-grouped): rows, weights and the partial slab must be 16-byte aligned "
+                                          "with widths that are multiples of 4"};
+  if (p.b_act && !(bf16 && p.prec == 1 && !wgrad && fast))
+    return GemmRoute{LOTUS_E_UNSUPPORTED, "lotus_linear: bf16 weight shadows (precision 5) need the bf16-storage build and 16-byte "
+                                          "aligned operands whose widths are multiples of 4"};
+  if (bf16 && p.prec == 3)  // (the entry points refuse it first)
+    return GemmRoute{LOTUS_E_UNSUPPORTED, "lotus_gemm: bf16x3 operands (precision 3) are not built for bf16 activation storage"};
+
+  // ---- gemm_kernel, 64 x 64 tiles.  Element types: A is always an activation; B is the weight matrix (fp32 master, or its bf16
+  // shadow) except in the weight gradient (both operands are activations); C is an activation except for the weight gradient
+  // and for split-K partial slabs (p.c_float).  In the fp32 build every combination is <float, float, float>.
+  r.family = 1; r.bm = r.bn = 64; r.epi = 0;
+  r.fast = fast; r.fused = fast && r.fused;
+  r.eb_act = wgrad || p.b_act; r.ec_float = wgrad || p.c_float;
+  r.grid = dim3(cdiv(p.N, 64), cdiv(p.M, 64), nz);
+  if (p.prec && fast) {
+    // bf16 / bf16x3 operands, converted while staged (weight gradients: bias sums from the fp32 registers).  bf16 storage: one
+    // bf16 MFMA covers 16 k, so a 32-deep slab is two MFMAs per wave between barriers and the block pays one global-load round
+    // trip per slab; the staging ring keeps four slabs in flight where the grid is small enough to afford its registers.
+    r.prec = p.prec; r.bk = 32;
+    r.depth = bf16 && (wgrad ? p.K : p.M) <= kBf16RingMaxRows ? 4 : 1;
+    r.name = wgrad ? "lotus_gemm(bf16 wgrad)" : "lotus_gemm(bf16)";
+  } else if (bf16) {
+    // bf16-storage build: the exact-fp32 product only serves the shapes the vectorised bf16 path cannot take (odd widths such
+    // as the 90- and 217-wide head layers)
+    r.bk = 32; r.depth = 1; r.name = "lotus_gemm";
   } else {
     // (tap-grouped products: about half of the row tiles leave at once — the grid the heuristics should see is the active one)
-    const long blocks_eff = p.tap_rows ? blocks64 / 2 : blocks64;
-    const int bk = SUM_A ? 32 : (blocks_eff * nz <= 512 ? 64 : (blocks_eff * nz <= 2048 ? 32 : 16));
-    const int rd = SUM_A ? 1 : (blocks_eff * nz <= kF32RingMaxBlocks ? 2 : 1);
-    if (p.tap_rows) {
-      if constexpr (A_KC && !SUM_A && FAST && !LOTUS_ACT_IS_BF16) {
-        lotus_note_dense_route(1, 64, 64, bk, nz, FAST, 0, 2);
-        if (bk == 64) LOTUS_LAUNCH((gemm_kernel<64, 64, 64, A_KC, B_KC, SUM_A, FAST, 0, act_t, float, float, 2, true>), g64, block, 0, st, p);
-        else if (bk == 32) LOTUS_LAUNCH((gemm_kernel<64, 64, 32, A_KC, B_KC, SUM_A, FAST, 0, act_t, float, float, 2, true>), g64, block, 0, st, p);
-        else LOTUS_LAUNCH((gemm_kernel<64, 64, 16, A_KC, B_KC, SUM_A, FAST, 0, act_t, float, float, 2, true>), g64, block, 0, st, p);
-        LOTUS_LAUNCH_CHECK("lotus_gemm(tap-grouped)");
-        return LOTUS_OK;
-      } else {
-        lotus_set_error("lotus_gemm: tap-grouped products need k-contiguous, 16-byte aligned fp32 rows");
-        return LOTUS_E_UNSUPPORTED;
-      }
-    }
-    if (rd == 2 && bk == 64) GEMM_GO_RD(64, 64, 64, 0, g64, 2);
-    else if (rd == 2 && bk == 16) GEMM_GO_RD(64, 64, 16, 0, g64, 2);
-    else if (rd == 2) GEMM_GO_RD(64, 64, 32, 0, g64, 2);
-    else if (bk == 64) GEMM_GO(64, 64, 64, 0, g64);
-    else if (bk == 32) GEMM_GO(64, 64, 32, 0, g64);
-    else GEMM_GO(64, 64, 16, 0, g64);
+    const long blocks = (long)r.grid.x * r.grid.y / (r.tap ? 2 : 1) * nz;
+    r.bk = wgrad ? 32 : (blocks <= 512 ? 64 : (blocks <= 2048 ? 32 : 16));
+    r.depth = wgrad ? 1 : (r.tap || blocks <= kF32RingMaxBlocks ? 2 : 1);
+    r.name = r.tap ? "lotus_gemm(tap-grouped)" : "lotus_gemm";
   }
-  LOTUS_LAUNCH_CHECK("lotus_gemm");
+  return r;
+}
+
+// ---- the launch of a family-1 route.  Every gemm_kernel instantiation of the library is named in gemm_go, once; the functions
+// below it turn the route's run-time fields into template arguments, one stage each, and instantiate only the forms gemm_route
+// returns (DESIGN.md section 4 lists the forms that went with the old dispatcher and why no call reached them).
+template <bool A_KC_, bool B_KC_, bool SUM_A_, bool FAST_, int PREC_, bool TAP_>
+struct GemmForm {
+  static constexpr bool A_KC = A_KC_, B_KC = B_KC_, SUM_A = SUM_A_, FAST = FAST_, TAP = TAP_;
+  static constexpr int PREC = PREC_;
+};
+template <typename F, int BK, int RD, typename EB, typename EC>
+static void gemm_go(const GemmRoute& r, const GemmP& p, hipStream_t st) {
+  LOTUS_LAUNCH((gemm_kernel<64, 64, BK, F::A_KC, F::B_KC, F::SUM_A, F::FAST, F::PREC, act_t, EB, EC, RD, F::TAP>), r.grid, dim3(256), 0, st, p);
+}
+template <typename F, int BK, int RD>
+static void gemm_go_types(const GemmRoute& r, const GemmP& p, hipStream_t st) {
+  if constexpr (!LOTUS_ACT_IS_BF16) {
+    gemm_go<F, BK, RD, float, float>(r, p, st);
+  } else if constexpr (F::SUM_A) {
+    gemm_go<F, BK, RD, act_t, float>(r, p, st);
+  } else {
+    if constexpr (F::PREC == 1) {  // (only the bf16 product reads a bf16 weight shadow: half the weight bytes, no conversion)
+      if (r.eb_act) return r.ec_float ? gemm_go<F, BK, RD, act_t, float>(r, p, st) : gemm_go<F, BK, RD, act_t, act_t>(r, p, st);
+    }
+    return r.ec_float ? gemm_go<F, BK, RD, float, float>(r, p, st) : gemm_go<F, BK, RD, float, act_t>(r, p, st);
+  }
+}
+template <typename F>
+static void gemm_go_slab(const GemmRoute& r, const GemmP& p, hipStream_t st) {
+  if constexpr (LOTUS_ACT_IS_BF16 && F::PREC == 1) {
+    if (r.depth == 4) gemm_go_types<F, 32, 4>(r, p, st);
+    else gemm_go_types<F, 32, 1>(r, p, st);
+  } else if constexpr (LOTUS_ACT_IS_BF16 || F::PREC || F::SUM_A) {
+    gemm_go_types<F, 32, 1>(r, p, st);
+  } else {  // exact fp32 products: no ring only on grids whose slabs are 16 deep, never with tap-grouped rows
+    if (r.depth == 1) { if constexpr (!F::TAP) gemm_go_types<F, 16, 1>(r, p, st); }
+    else if (r.bk == 64) gemm_go_types<F, 64, 2>(r, p, st);
+    else if (r.bk == 32) gemm_go_types<F, 32, 2>(r, p, st);
+    else gemm_go_types<F, 16, 2>(r, p, st);
+  }
+}
+template <bool A_KC, bool B_KC, bool SUM_A>
+static void gemm_go_mode(const GemmRoute& r, const GemmP& p, hipStream_t st) {
+  if (r.tap) {
+    if constexpr (!SUM_A && !LOTUS_ACT_IS_BF16) gemm_go_slab<GemmForm<A_KC, B_KC, SUM_A, true, 0, true>>(r, p, st);
+  } else if (r.prec == 1) {
+    gemm_go_slab<GemmForm<A_KC, B_KC, SUM_A, true, 1, false>>(r, p, st);
+  } else if (r.prec == 3) {
+    if constexpr (!LOTUS_ACT_IS_BF16) gemm_go_slab<GemmForm<A_KC, B_KC, SUM_A, true, 3, false>>(r, p, st);
+  } else if (r.fast) {
+    gemm_go_slab<GemmForm<A_KC, B_KC, SUM_A, true, 0, false>>(r, p, st);
+  } else {
+    gemm_go_slab<GemmForm<A_KC, B_KC, SUM_A, false, 0, false>>(r, p, st);
+  }
+}
+static int gemm_launch(const GemmRoute& r, const GemmP& p, hipStream_t st) {
+  gemm_note(r);
+  if (r.layout == GEMM_FWD) gemm_go_mode<true, true, false>(r, p, st);
+  else if (r.layout == GEMM_DGRAD) gemm_go_mode<true, false, false>(r, p, st);
+  else gemm_go_mode<false, false, true>(r, p, st);
+  LOTUS_LAUNCH_CHECK(r.name);
   return LOTUS_OK;
 }
 
-// FAST needs float4-safe extents on both operands: the contiguous dimension must be a multiple of 4
-// (K for k-contiguous operands, M / N otherwise) and at least 4 wide
-template <bool A_KC, bool B_KC>
-static bool fast_ok(const GemmP& p) {
-  const bool a_ok = p.a_vec && (A_KC ? (p.K % 4 == 0 && p.K >= 4) : (p.M % 4 == 0 && p.M >= 4));
-  const bool b_ok = p.b_vec && (B_KC ? (p.K % 4 == 0 && p.K >= 4) : (p.N % 4 == 0 && p.N >= 4));
-  const bool c_ok = p.N % 4 == 0 && p.ldc % 4 == 0 && p.part_stride % 4 == 0 && vec_ok(p.C, p.ldc) &&
-                    (!p.bias || ((uintptr_t)p.bias) % 16 == 0) && (!p.residual || ((uintptr_t)p.residual) % 16 == 0) &&
-                    (!p.pre || ((uintptr_t)p.pre) % 16 == 0) && (!p.mulpre || ((uintptr_t)p.mulpre) % 16 == 0) &&
-                    (!p.part || ((uintptr_t)p.part) % 16 == 0);
-  return a_ok && b_ok && c_ok;
-}
-
-template <bool A_KC, bool B_KC, bool SUM_A>
-static int launch_gemm(GemmP& p, int nz, hipStream_t st) {
-  const bool a_ok = p.a_vec && (A_KC ? (p.K % 4 == 0 && p.K >= 4) : (p.M % 4 == 0 && p.M >= 4));
-  const bool b_ok = p.b_vec && (B_KC ? (p.K % 4 == 0 && p.K >= 4) : (p.N % 4 == 0 && p.N >= 4));
-  const bool c_ok = p.N % 4 == 0 && p.ldc % 4 == 0 && p.part_stride % 4 == 0 && vec_ok(p.C, p.ldc) &&
-                    (!p.bias || ((uintptr_t)p.bias) % 16 == 0) && (!p.residual || ((uintptr_t)p.residual) % 16 == 0) &&
-                    (!p.pre || ((uintptr_t)p.pre) % 16 == 0) && (!p.mulpre || ((uintptr_t)p.mulpre) % 16 == 0);
-  if (a_ok && b_ok && c_ok) {
-    if constexpr (A_KC || SUM_A) {  // tall products: the LDS-DMA kernels (gemm_dma.hip) where they apply
-      const int rc = launch_gemm_dma(p, A_KC ? (B_KC ? 0 : 1) : 2, nz, st);
-      if (rc != LOTUS_GEMM_DMA_NA) return rc;
-    }
-    return launch_gemm_t<A_KC, B_KC, SUM_A, true>(p, nz, st);
+// a route's refusal, or its launch
+static int gemm_dispatch(const GemmRoute& r, const GemmP& p, hipStream_t st) {
+  if (r.rc) {
+    if (r.error) lotus_set_error("%s", r.error);
+    return r.rc;
   }
-  return launch_gemm_t<A_KC, B_KC, SUM_A, false>(p, nz, st);
+  return r.family == 1 ? gemm_launch(r, p, st) : gemm_dma_launch(r, p, st);
 }
+static int gemm_run(const GemmP& p, int layout, int nz, hipStream_t st) { return gemm_dispatch(gemm_route(p, layout, nz, gemm_dma_env()), p, st); }
 
 static void set_drop(GemmP& p, float drop_p, unsigned long long seed) {
   p.drop_seed = seed;
@@ -806,26 +882,25 @@ static bool splitk_fused_enabled() {
   return on != 0;
 }
 
-template <bool A_KC, bool B_KC>
-static int run_gemm_splitk(GemmP& p, void* workspace, size_t workspace_bytes, unsigned* counters, hipStream_t st) {
+static int run_gemm_splitk(GemmP& p, int layout, void* workspace, size_t workspace_bytes, unsigned* counters, hipStream_t st) {
   if (!splitk_fused_enabled()) counters = nullptr;
   const int nz = (p.N % 4 == 0 && p.ldc == p.N) ? fwd_splits(p.M, p.N, p.K) : 1;
   const size_t need = (size_t)nz * p.M * p.N * sizeof(float);
-  if (nz == 1 || !workspace || workspace_bytes < need || ((uintptr_t)workspace) % 16) return launch_gemm<A_KC, B_KC, false>(p, 1, st);
+  if (nz == 1 || !workspace || workspace_bytes < need || ((uintptr_t)workspace) % 16) return gemm_run(p, layout, 1, st);
   const int klen = cdiv(cdiv(p.K, nz), GEMM_KALIGN) * GEMM_KALIGN;
   const long tiles = (long)cdiv(p.M, 64) * cdiv(p.N, 64);
   if (counters && tiles <= LOTUS_SPLITK_MAX_TILES) {
     // one launch: partials + last-arrival reduction with the full epilogue
     GemmP q = p;
     q.part = (float*)workspace; q.part_stride = (long)p.M * p.N; q.cnt = counters; q.klen = klen;
-    if (fast_ok<A_KC, B_KC>(q)) return launch_gemm<A_KC, B_KC, false>(q, nz, st);
+    if (gemm_fast_ok(q, layout)) return gemm_run(q, layout, nz, st);
   }
   GemmP q = p;
   q.C = workspace; q.c_float = 1; q.part_stride = (long)p.M * p.N;
   q.bias = nullptr; q.residual = nullptr; q.pre = nullptr; q.mulpre = nullptr; q.act = LOTUS_ACT_NONE; q.drop_thresh = 0;
   q.klen = klen;
   StopEventOnLast stop_ev;
-  int rc = launch_gemm<A_KC, B_KC, false>(q, nz, st);
+  int rc = gemm_run(q, layout, nz, st);
   if (rc) return rc;
   const long total4 = (long)p.M * p.N / 4;
   int g = cdiv(total4, 256);
@@ -857,17 +932,22 @@ int lotus_conv_tap_gemm(int mode, const act_t* x, const float* w, float* part, c
     p.drop_inv_keep = 1.f;
     p.a_rows = tg_in; p.tap_cnt = tg_cnt; p.tap_rows = n64; p.b_tap_mirror = mode == 1; p.b_tap_stride = cin;
     p.a_src_rows = src_rows;
-    {  // the LDS-DMA tiles where they apply (gemm_dma.h, gemm_dma_tap_kernel); else the 64 x 64 kernel below
-      GemmP q = p;
-      const int rc = launch_gemm_dma_tap(q, mode, st);
-      if (rc != LOTUS_GEMM_DMA_NA) return rc;
-    }
-    if (!(fast_ok<true, true>(p))) {
-      lotus_set_error("lotus_subm_conv(tap-grouped): rows, weights and the partial slab must be 16-byte aligned with widths that are multiples of 4");
-      return LOTUS_E_UNSUPPORTED;
-    }
-    return mode == 0 ? launch_gemm<true, true, false>(p, 1, st) : launch_gemm<true, false, false>(p, 1, st);
+    // the LDS-DMA tiles where they apply (gemm_dma.h, gemm_dma_tap_kernel: the reduction in one range); else the 64 x 64 kernel
+    const GemmRoute r = gemm_route(p, mode == 0 ? GEMM_FWD : GEMM_DGRAD, 1, gemm_dma_env());
+    if (r.family == 3) p.klen = p.K;
+    return gemm_dispatch(r, p, st);
   }
+}
+
+// The `precision` argument of entry point `fn`: 0, 1 or 3 (3 not with bf16 storage).  5 (bf16-storage build only) = precision 1
+// with `w` pointing at a bf16 shadow of the weights; a weight gradient reads none (w_shadow null) and takes 5 as 1.
+static int check_precision(const char* fn, int& precision, int* w_shadow) {
+  if (w_shadow) *w_shadow = precision == 5;
+  LOTUS_CHECK_ARG(!(w_shadow && *w_shadow) || LOTUS_ACT_IS_BF16, "%s: precision 5 (bf16 weight shadow) exists in the bf16-storage build only", fn);
+  if (precision == 5) precision = 1;
+  LOTUS_CHECK_ARG(precision == 0 || precision == 1 || precision == 3, "%s: precision must be 0, 1 or 3%s", fn, w_shadow ? " (5 with bf16 weights)" : "");
+  LOTUS_CHECK_ARG(!(LOTUS_ACT_IS_BF16 && precision == 3), "%s: bf16x3 operands (precision 3) are not built for bf16 activation storage; use 1 (bf16) or 0", fn);
+  return LOTUS_OK;
 }
 
 extern "C" {
@@ -888,12 +968,8 @@ int lotus_linear_fwd(const act_t* x, const float* w, const float* bias, const ac
                      act_t* pre, int M, int N, int K, int act, float drop_p, unsigned long long drop_seed,
                      int precision, void* workspace, size_t workspace_bytes, void* counters, void* stream) {
   LOTUS_CHECK_ARG(x && w && y && M >= 0 && N > 0 && K > 0, "lotus_linear_fwd: bad arguments");
-  // precision 5 (bf16-storage build only) = precision 1 with `w` pointing at a bf16 shadow of the weights
-  const int w_shadow = precision == 5;
-  LOTUS_CHECK_ARG(!w_shadow || LOTUS_ACT_IS_BF16, "lotus_linear_fwd: precision 5 (bf16 weight shadow) exists in the bf16-storage build only");
-  if (w_shadow) precision = 1;
-  LOTUS_CHECK_ARG(precision == 0 || precision == 1 || precision == 3, "lotus_linear_fwd: precision must be 0, 1 or 3 (5 with bf16 weights)");
-  LOTUS_CHECK_ARG(!(LOTUS_ACT_IS_BF16 && precision == 3), "lotus_linear_fwd: bf16x3 operands (precision 3) are not built for bf16 activation storage; use 1 (bf16) or 0");
+  int w_shadow;
+  if (const int rc = check_precision("lotus_linear_fwd", precision, &w_shadow)) return rc;
   if (M == 0) return LOTUS_OK;
   GemmP p;
   memset(&p, 0, sizeof(p));
@@ -903,7 +979,7 @@ int lotus_linear_fwd(const act_t* x, const float* w, const float* bias, const ac
   p.klen = cdiv(K, GEMM_KALIGN) * GEMM_KALIGN;
   p.a_vec = vec_ok(x, K); p.b_vec = vec_ok(w, K); p.prec = precision; p.b_act = w_shadow;
   set_drop(p, drop_p, drop_seed);
-  return run_gemm_splitk<true, true>(p, workspace, workspace_bytes, (unsigned*)counters, (hipStream_t)stream);
+  return run_gemm_splitk(p, GEMM_FWD, workspace, workspace_bytes, (unsigned*)counters, (hipStream_t)stream);
 }
 
 // dx = (dy w) * act'(pre) * dropmask + add.   dy [M,N], w [N,K], dx/pre/add [M,K].
@@ -913,12 +989,8 @@ int lotus_linear_dgrad(const act_t* dy, const float* w, act_t* dx, const act_t* 
                        int N, int K, int act, float drop_p, unsigned long long drop_seed, int precision, void* workspace,
                        size_t workspace_bytes, void* counters, void* stream) {
   LOTUS_CHECK_ARG(dy && w && dx && M >= 0 && N > 0 && K > 0, "lotus_linear_dgrad: bad arguments");
-  // precision 5 (bf16-storage build only) = precision 1 with `w` pointing at a bf16 shadow of the weights
-  const int w_shadow = precision == 5;
-  LOTUS_CHECK_ARG(!w_shadow || LOTUS_ACT_IS_BF16, "lotus_linear_dgrad: precision 5 (bf16 weight shadow) exists in the bf16-storage build only");
-  if (w_shadow) precision = 1;
-  LOTUS_CHECK_ARG(precision == 0 || precision == 1 || precision == 3, "lotus_linear_dgrad: precision must be 0, 1 or 3 (5 with bf16 weights)");
-  LOTUS_CHECK_ARG(!(LOTUS_ACT_IS_BF16 && precision == 3), "lotus_linear_dgrad: bf16x3 operands (precision 3) are not built for bf16 activation storage; use 1 (bf16) or 0");
+  int w_shadow;
+  if (const int rc = check_precision("lotus_linear_dgrad", precision, &w_shadow)) return rc;
   if (M == 0) return LOTUS_OK;
   GemmP p;
   memset(&p, 0, sizeof(p));
@@ -929,7 +1001,7 @@ int lotus_linear_dgrad(const act_t* dy, const float* w, act_t* dx, const act_t* 
   p.klen = cdiv(N, GEMM_KALIGN) * GEMM_KALIGN;
   p.a_vec = vec_ok(dy, N); p.b_vec = vec_ok(w, K); p.prec = precision; p.b_act = w_shadow;
   set_drop(p, drop_p, drop_seed);
-  return run_gemm_splitk<true, false>(p, workspace, workspace_bytes, (unsigned*)counters, (hipStream_t)stream);
+  return run_gemm_splitk(p, GEMM_DGRAD, workspace, workspace_bytes, (unsigned*)counters, (hipStream_t)stream);
 }
 
 // The input gradient of a linear layer whose INPUT is a LayerNorm output, together with that LayerNorm's backward:
@@ -961,10 +1033,8 @@ int lotus_linear_dgrad_ln(const act_t* dy, const float* w, const act_t* x, const
     p.a_vec = vec_ok(dy, N); p.b_vec = vec_ok(w, K); p.prec = 0;
     set_drop(p, dz ? dz_p : 0.f, dz_seed);
     p.ln_x = x; p.ln_mean = mean; p.ln_rstd = rstd; p.ln_gamma = gamma; p.ln_part = (float*)ln_workspace; p.ln_dz = dz;
-    if (p.a_vec && p.b_vec && vec_ok(dx, K) && vec_ok(x, K) && (!add || vec_ok(add, K))) {
-      const int rc = launch_gemm_dma(p, 1, 1, (hipStream_t)stream);
-      if (rc != LOTUS_GEMM_DMA_NA) { *nparts = cdiv(M, 128); return rc; }
-    }
+    const int rc = gemm_run(p, GEMM_DGRAD, 1, (hipStream_t)stream);
+    if (rc != LOTUS_GEMM_NA) { *nparts = cdiv(M, 128); return rc; }
   }
   StopEventOnLast stop_ev;  // (an armed stop event belongs to the LAST launch: the LayerNorm backward)
   int rc = lotus_linear_dgrad(dy, w, dn, nullptr, nullptr, M, N, K, LOTUS_ACT_NONE, 0.f, 0, precision, workspace, workspace_bytes, counters, stream);
@@ -985,7 +1055,7 @@ int lotus_dense_last_route(int* out) {
 }
 
 static int wgrad_splits(int M, int N, int K) {
-  if (const int dz = gemm_dma_wgrad_splits(M, N, K)) return dz;  // tall products on the LDS-DMA kernels: their own tiling
+  if (const int dz = gemm_dma_wgrad_splits(M, N, K, gemm_dma_env())) return dz;  // tall products on the LDS-DMA kernels: their own tiling
   int nz = 1;
   const long tiles = (long)cdiv(N, 64) * cdiv(K, 64);
   if (tiles >= 128 && M < 1024) return 1;  // deep levels: the second (reduce) launch costs more than it hides
@@ -1005,9 +1075,7 @@ int lotus_linear_wgrad(const act_t* dy, const act_t* x, float* dw, float* db, in
                        int accumulate, int precision, void* workspace, size_t workspace_bytes, void* counters,
                        void* stream) {
   LOTUS_CHECK_ARG(dy && x && dw && M >= 0 && N > 0 && K > 0, "lotus_linear_wgrad: bad arguments");
-  if (precision == 5) precision = 1;  // (the shadow flag of the forward / input-gradient products: no weights are read here)
-  LOTUS_CHECK_ARG(precision == 0 || precision == 1 || precision == 3, "lotus_linear_wgrad: precision must be 0, 1 or 3");
-  LOTUS_CHECK_ARG(!(LOTUS_ACT_IS_BF16 && precision == 3), "lotus_linear_wgrad: bf16x3 operands (precision 3) are not built for bf16 activation storage; use 1 (bf16) or 0");
+  if (const int rc = check_precision("lotus_linear_wgrad", precision, nullptr)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int nz = wgrad_splits(M, N, K);
   const size_t slab = (size_t)N * K + N;
@@ -1031,7 +1099,7 @@ int lotus_linear_wgrad(const act_t* dy, const act_t* x, float* dw, float* db, in
     GemmP q = p;
     q.C = dw; q.part = part; q.part_stride = (long)slab; q.cnt = (unsigned*)counters;
     q.bias_part = db ? part + (size_t)N * K : nullptr; q.bias_stride = (long)slab; q.bias_out = db; q.accumulate = accumulate;
-    if (fast_ok<false, false>(q)) return launch_gemm<false, false, true>(q, nz, st);
+    if (gemm_fast_ok(q, GEMM_WGRAD)) return gemm_run(q, GEMM_WGRAD, nz, st);
   }
   if (direct) {
     p.C = dw; p.bias_part = db;
@@ -1039,7 +1107,7 @@ int lotus_linear_wgrad(const act_t* dy, const act_t* x, float* dw, float* db, in
     p.C = part; p.part_stride = (long)slab;
     p.bias_part = db ? part + (size_t)N * K : nullptr; p.bias_stride = (long)slab;
   }
-  int rc = launch_gemm<false, false, true>(p, nz, st);
+  int rc = gemm_run(p, GEMM_WGRAD, nz, st);
   if (rc || direct) return rc;
   const long n = (long)N * K;
   if (db && db == dw + n) return lotus_reduce_parts(part, dw, (long)slab, (long)slab, nz, accumulate, st);

@@ -135,7 +135,7 @@ __device__ __forceinline__ void gemm_epilogue4(const GemmP& p, TC* __restrict__ 
 // The tail of a fused split-K block (after its raw partial tile and bias partial have been stored): release the partial
 // (agent scope: the other splits of the tile may run on another XCD / L2), count the arrival, and let the LAST block of the
 // tile sum the nz partials in fixed z order and apply the epilogue.  All reads come after the acquire fence.  Shared by
-// gemm_kernel and wgrad_stream_kernel.
+// gemm_kernel and gemm_dma_kernel.
 template <bool SUM_A, int BM, int BN, typename EC>
 __device__ __forceinline__ void splitk_fused_tail(const GemmP& p, int bx, int by, int m0, int n0, int tid) {
   __shared__ int s_last;
@@ -185,10 +185,30 @@ __device__ __forceinline__ void splitk_fused_tail(const GemmP& p, int bx, int by
   if (tid == 0) p.cnt[tile_id] = 0;  // ready for the next launch on this stream
 }
 
-// gemm_dma.hip: the LDS-DMA kernels for tall products (returns LOTUS_GEMM_DMA_NA when a product is not theirs)
-#define LOTUS_GEMM_DMA_NA (-100)
-int launch_gemm_dma(GemmP& p, int layout, int nz, hipStream_t st);
-int gemm_dma_wgrad_splits(int M, int N, int K);
-int launch_gemm_dma_tap(GemmP& p, int layout, hipStream_t st);
+// Which kernel a prepared product runs on and how it is launched: the answer of gemm_route() (gemm.hip: the one place that
+// decides).  gemm_launch (gemm.hip: gemm_kernel) and gemm_dma_launch (gemm_dma.hip: the LDS-DMA kernels, their own translation
+// unit for its compiler flag) write the route record, name the kernels and launch; neither decides anything.
+enum { GEMM_FWD = 0, GEMM_DGRAD = 1, GEMM_WGRAD = 2 };  // operand layouts; a tap-grouped product (p.tap_rows) is FWD or DGRAD
+#define LOTUS_GEMM_NA (-100)  // GemmRoute::rc: no kernel takes this product (the LayerNorm epilogue off the LDS-DMA tiles)
+struct GemmRoute {
+  int rc;             // LOTUS_OK: launch what follows; else the refusal's return code, `error` its text (null: LOTUS_GEMM_NA)
+  const char* error;
+  int family;         // 1 gemm_kernel, 2 gemm_dma_kernel, 3 gemm_dma_tap_kernel
+  int layout;         // GEMM_*
+  int bm, bn, bk;
+  int depth;          // staging-ring depth (family 1) or LDS stages (2, 3)
+  int fast, fused;    // float4 accesses without guards; split-K summed by the last block of a tile
+  int prec;           // operand precision of the kernel: 0 fp32, 1 bf16, 3 bf16x3
+  int eb_act, ec_float;  // element types (EA is act_t): EB act_t instead of float, EC float instead of act_t (bf16 storage only)
+  int epi;            // gemm_dma_kernel: 0 plain store, 1 full epilogue, 2 LayerNorm backward
+  int tap;            // tap-grouped rows
+  int nz;
+  dim3 grid;
+  const char* name;   // of the launch, in a launch failure's message
+};
+static inline void gemm_note(const GemmRoute& r) {
+  lotus_note_dense_route(r.family, r.bm, r.bn, r.bk, r.nz, r.fast, r.fused, r.depth);
+}
+int gemm_dma_launch(const GemmRoute& r, const GemmP& p, hipStream_t st);
 
 }  // namespace LOTUS_NS

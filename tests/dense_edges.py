@@ -167,7 +167,7 @@ FEW_WGRAD_ROWS = {1024: 8, 1061: 8, 2085: 16}    # rows -> ranges under the defa
 
 def _few_cases():
     """Few rows on both tiles of gemm_dma_kernel.  `route` holds under FEW_ENV; opts["default"] is the route of the same call
-    without the switches.  The LayerNorm epilogue needs 128 row tiles whatever the switches say (launch_gemm_dma refuses: the
+    without the switches.  The LayerNorm epilogue needs 128 row tiles whatever the switches say (gemm_route refuses: the
     call then is lotus_linear_dgrad — on the LDS-DMA tile of its width under FEW_ENV — and lotus_layernorm_bwd).  So the
     EPI = 2 kernel never runs on few rows; what the few-dgrad_ln_two_launch rows assert is that refusal: family 2 is the
     plain product, `dn` holds dy w and nparts is lotus_layernorm_bwd_parts(M, K), not ceil(M / 128) by construction."""
@@ -227,6 +227,32 @@ def _twin_cases():
     return out
 
 
+# gemm_kernel's thresholds, in 64 x 64 output tiles: slabs 64 deep up to 512 tiles, 32 up to 2048, 16 above; the two-slab
+# register ring up to 8192 tiles.  (rows, output width) on the threshold | the first grid past it -> slab depth, ring depth
+BOUND_TILES = {512: (((32768, 64), 64, 2), ((32769, 64), 32, 2)),
+               2048: (((8192, 1024), 32, 2), ((8192, 1088), 16, 2)),
+               8192: (((8192, 4096), 16, 2), ((8192, 4160), 16, 1))}
+B16_RING_MAX_ROWS = 8192    # the twin's four-slab ring: products over <= 8192 rows
+
+
+def _bound_cases():
+    """Host-only rows (not in TABLE: the GPU tests do not run them) on each side of every threshold of gemm_kernel's slab and
+    ring depth.  A reduction of 8 and fewer than 400 128-row tiles keep the rows off the LDS-DMA kernels.  The twin's ring goes
+    by the rows of the activation operand: M of a forward / input-gradient product, the reduction of a weight gradient (64
+    ranges of 128 rows here)."""
+    out = []
+    for pair in BOUND_TILES.values():
+        for (rows, o), bk, depth in pair:
+            for call in ("fwd", "dgrad"):
+                out.append(Case(f"bound-{call}-{rows}x{o}x8", call, *_mnk(call, rows, o, 8), dict(depth=depth), _gk(bk)))
+    for rows, depth in ((B16_RING_MAX_ROWS, 4), (B16_RING_MAX_ROWS + 1, 1)):
+        t = dict(b16=1, prec=1, depth=depth)
+        for call in ("fwd", "dgrad"):
+            out.append(Case(f"bound-b16-{call}-{rows}x64x64", call, rows, 64, 64, dict(t), _gk(32)))
+        out.append(Case(f"bound-b16-wgrad-{rows}x64x64", "wgrad", rows, 64, 64, dict(t, bias=1), _gk(32, nz=64)))
+    return out
+
+
 def default_route(case):
     """The route of `case` in a process without FEW_ENV."""
     return case.opts.get("default", case.route)
@@ -240,6 +266,7 @@ DMA = _dma_cases()
 FEW = _few_cases()
 TAIL = _tail_cases()
 TWIN = _twin_cases()
+BOUNDS = _bound_cases()
 TABLE = GRID + SPLIT + WGRAD + PRECISION + DMA + FEW + TAIL + TWIN
 BY_ID = {c.id: c for c in TABLE}
 assert len(BY_ID) == len(TABLE)

@@ -64,7 +64,7 @@ def call_on_host(L, case):
     return rc, _route(L, de.entry(case, "lotus_dense_last_route")), nparts
 
 
-@pytest.mark.parametrize("group", ["GRID", "SPLIT", "WGRAD", "PRECISION", "DMA", "FEW", "TAIL", "TWIN"])
+@pytest.mark.parametrize("group", ["GRID", "SPLIT", "WGRAD", "PRECISION", "DMA", "FEW", "TAIL", "TWIN", "BOUNDS"])
 def test_every_row_of_the_table_takes_its_route(lib, group):
     cases = getattr(de, group)
     assert cases
@@ -93,6 +93,15 @@ def test_the_table_holds_what_it_says():
     assert all(c.route.family == 2 for c in de.DMA + de.FEW) and all(c.route.family == 1 for c in de.GRID + de.SPLIT + de.WGRAD + de.PRECISION + de.TAIL + de.TWIN)
     assert all(de.default_route(c).family == 1 for c in de.FEW)
     assert {(c.call, c.M, c.opts["prec"]) for c in de.TWIN if c.M != 228 and c.route.fast} == {(call, m, p) for call in ("fwd", "dgrad", "wgrad") for m in (5, 64, 65) for p in (0, 1)}
+    # BOUNDS: for both calls the grid of 64 x 64 output tiles exactly on each of gemm_kernel's three thresholds and the first
+    # grid past it (one more row tile or one more column tile); the twin's ring threshold on both sides for every call
+    for call in ("fwd", "dgrad"):
+        grids = {(-(-c.M // 64), -(-(c.N if call == "fwd" else c.K) // 64)) for c in de.BOUNDS if c.call == call and not c.opts.get("b16")}
+        for t in (512, 2048, 8192):
+            on = {g for g in grids if g[0] * g[1] == t}
+            assert on and any((r + 1, c) in grids or (r, c + 1) in grids for r, c in on), (call, t)
+    assert {(c.call, c.M) for c in de.BOUNDS if c.opts.get("b16")} == {(call, m) for call in ("fwd", "dgrad", "wgrad") for m in (8192, 8193)}
+    assert not set(c.id for c in de.BOUNDS) & set(de.BY_ID)
 
 
 def test_the_record_is_the_last_product_and_has_a_twin(lib):

@@ -1,6 +1,6 @@
 """The LDS-DMA dense kernels (csrc/gemm_dma.h, round 5) and the tall products around them.
 
-What runs where: the dispatcher (csrc/gemm_dma.hip) gives these kernels exact-fp32 products of >= 16 384 rows on 16-byte
+What runs where: the dispatcher (gemm_route, csrc/gemm.hip) gives these kernels exact-fp32 products of >= 16 384 rows on 16-byte
 aligned operands, forward and input gradients only when their 128-row tiles make >= 400 blocks (>= 128 with the LayerNorm
 epilogue), weight gradients only when ~256 blocks leave >= 256 rows per split.  Of the shape lists below that is
   forward            (17003, 512, 128) alone; the other seven — (16411, 128, 48), (16385, 256, 16), (16384, 64, 96) among them —
