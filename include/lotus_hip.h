@@ -749,6 +749,28 @@ int lotus_ctx_taps_bwd(const float* dy, const int* nbr, const int* off, float* d
  * backward grid, rows per presence tile forward, backward, the widest C the entry points take at this T}.  Refuses what they refuse. */
 int lotus_ctx_taps_plan(int n, int B, int T, int C, int* out);
 
+/* ---- coordinate term of SerializedAttention, add_coords_in_attn 'qk' / 'qkv' (fp32 only, no bf16 twin) -------------------------
+ * PointTransformerV3/model.py:484-495 (coords_proj = nn.Linear(3, channels, bias=False), model.py:396-398): 'qkv' adds
+ * coords_proj(point.coord) to the normed rows before the qkv product, 'qk' adds it to the q and to the k columns of the product.
+ * P = coords_proj.weight [Cw][3]; coord: row i at coord + i coord_ld, three floats (coord_ld >= 3: 3 for a level's own coordinates,
+ * the width of pc_fts for its [:, :3] view).  W = Cw ('qkv': y = the normed rows, ld = Cw) or 2 Cw ('qk': y = [q | k | v], ld = 3 Cw).
+ *   lotus_coord_add_fwd:    y[i][j] += sum_k coord[i][k] P[j % Cw][k],  j < W, in place; columns >= W of a row are neither read
+ *                           nor written
+ *   lotus_coord_add_wgrad:  dP[c][k] = sum_i sum_{h: c + h Cw < W} dy[i][c + h Cw] coord[i][k]   (written, not accumulated)
+ * The weight gradient has no atomics: a thread sums at most `rows per thread` rows in fp32 at a time, everything above that — a
+ * thread's chunks, the threads of a block, the row ranges — is summed in float64 in ascending order; reruns are bit-identical.
+ * LOTUS_E_ARG before any launch on Cw <= 0, Cw % 4 != 0, Cw > 2048, W other than Cw or 2 Cw, n < 0, ld < W, ld % 4 != 0,
+ * coord_ld < 3, a null pointer, y / dy not 16-byte aligned or a short workspace.  n == 0: forward returns 0 without a launch, the
+ * weight gradient writes zeros. */
+size_t lotus_coord_add_workspace(int n, int W, int Cw);
+int lotus_coord_add_fwd(float* y, long ld, int W, int Cw, const float* coord, long coord_ld, const float* P, int n, void* stream);
+int lotus_coord_add_wgrad(const float* dy, long ld, int W, int Cw, const float* coord, long coord_ld, int n, float* dP,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* Diagnostic, host only: out[6] = {rows per block of the forward grid, its blocks for n rows, row ranges (splits) of the weight
+ * gradient, rows a thread sums in fp32 at a time, quad lanes and row lanes of its block (a range of at most row lanes x rows per
+ * thread rows is one fp32 chunk per thread; the splits stop growing at 256)}.  Refuses what the entry points refuse. */
+int lotus_coord_add_plan(int n, int W, int Cw, int* out);
+
 #ifdef __cplusplus
 }
 #endif

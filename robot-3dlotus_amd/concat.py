@@ -95,10 +95,10 @@ class CtxStemFn(torch.autograd.Function):
 class PlainBlock(Block):
     """model.py:586-680; qk_norm False registers attn.q_norm / k_norm as nn.Identity (model.py:393-394): no state entries."""
 
-    def __init__(self, c, h, mlp_ratio, qk_norm=True):
+    def __init__(self, c, h, mlp_ratio, qk_norm=True, coords=False):
         super().__init__(c, h, mlp_ratio)
-        if not qk_norm:
-            self.attn = _Attn(c, h, False)
+        if not qk_norm or coords:
+            self.attn = _Attn(c, h, qk_norm, coords)
 
 
 class PointTransformerV3Plain(PointTransformerV3CA):
@@ -106,6 +106,7 @@ class PointTransformerV3Plain(PointTransformerV3CA):
     takes data_dict["feat"] = pc [N, c_pc <= 8] and data_dict["stem_context"] = [B, pdnorm_context_channels];
     in_channels = c_pc + pdnorm_context_channels is the width of embedding.stem.conv.weight, as in the reference."""
     plain_attention = True
+    coord_attention = True
 
     def __init__(self, in_channels=6, *args, **kw):
         super().__init__(in_channels, *args, **kw)
@@ -133,7 +134,7 @@ class PointTransformerV3Plain(PointTransformerV3CA):
         return pdnorm_context_channels
 
     def _add_depth(self, stage, i, c, h, mlp_ratio):
-        stage.add_module(f"block{i}", PlainBlock(c, h, mlp_ratio, self.qk_norm))
+        stage.add_module(f"block{i}", PlainBlock(c, h, mlp_ratio, self.qk_norm, self.add_coords))
 
     def _index_sites(self):
         pass

@@ -198,6 +198,22 @@ CONCAT_OVERRIDES = {"concat_yaml": CONCAT_SWITCHES + ["ptv3_config.in_channels",
                     "concat_tiny": TINYCTX_OVERRIDES + CONCAT_SWITCHES + ["ptv3_config.in_channels", "263"]}
 
 
+# add_coords_in_attn 'qk' / 'qkv' (simple_policy_ptv3.yaml:129, motion_planner_ptv3.yaml:139: "none, qk, qkv"; PointTransformerV3/
+# model.py:484-495) on the AdaNorm and the Concat backbone.  'adanorm_yaml_qk' is the shipped YAML with that one key flipped; the
+# tiny ones cover both modes with and without q/k LayerNorm (adanorm_tiny_plain and mp_ada_tiny have qk_norm False, adanorm_tiny
+# and concat_tiny qk_norm True).
+def _coords(mode):
+    return ["ptv3_config.add_coords_in_attn", mode]
+
+
+ADANORM_OVERRIDES.update({"adanorm_tiny_qk": ADANORM_OVERRIDES["adanorm_tiny_plain"] + _coords("qk"),
+                          "adanorm_tiny_qkv": ADANORM_OVERRIDES["adanorm_tiny"] + _coords("qkv"),
+                          "adanorm_yaml_qk": _coords("qk")})
+CONCAT_OVERRIDES.update({"concat_tiny_qk": CONCAT_OVERRIDES["concat_tiny"] + _coords("qk"),
+                         "concat_tiny_qkv": CONCAT_OVERRIDES["concat_tiny"] + _coords("qkv")})
+MP_ADA_OVERRIDES["mp_ada_tiny_qkv"] = MP_ADA_OVERRIDES["mp_ada_tiny"] + _coords("qkv")
+
+
 def preset(name="v1"):
     """'v1' / 'tiny': 3D-LOTUS policy; 'peract': the RLBench-18task (PerAct) variant of BASELINE configs[4] (same network;
     its bf16 compute mode is ops.set_gemm_precision("bf16")); 'mp' / 'mp_tiny': 3D-LOTUS++ motion planner (configs[3]);
@@ -206,7 +222,9 @@ def preset(name="v1"):
     adanorm_tiny / adanorm_v1 with qk_norm False;
     'tiny_reg' / 'v1_reg' / 'adanorm_tiny_reg': their base preset with the regression head (heatmap_mlp positions, euler);
     'mp_yaml': motion_planner_ptv3.yaml as shipped (MotionPlannerPTV3AdaNorm, soft trajectory head); 'mp_ada_tiny': its tiny width;
-    'concat_yaml' / 'concat_tiny': SimplePolicyPTV3Concat on the YAML's networks (in_channels 262) / the tiny ones (263)."""
+    'concat_yaml' / 'concat_tiny': SimplePolicyPTV3Concat on the YAML's networks (in_channels 262) / the tiny ones (263);
+    'adanorm_tiny_qk' / 'adanorm_tiny_qkv' / 'adanorm_yaml_qk' / 'concat_tiny_qk' / 'concat_tiny_qkv' / 'mp_ada_tiny_qkv': their
+    base preset with add_coords_in_attn 'qk' / 'qkv' (adanorm_tiny_qk on adanorm_tiny_plain: qk_norm False)."""
     if name in ("mp", "mp_tiny", "mp_tinyctx"):
         model = copy.deepcopy(_YAML_MODEL)
         model["model_class"] = _YAML_MP_DELTA["model_class"]

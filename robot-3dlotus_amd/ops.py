@@ -1265,11 +1265,37 @@ def cpe_branch_bwd(dl, dy, xs, cw, lw, c, lvl, wt, same):
     return dy, dxs, dcw, dcb, dlw, dlb
 
 
-def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, attn_p, dpath):
+def coord_add_fwd(y, W, Cw, coord, cproj):
+    """In place: y[:, j] += (coord cproj^T)[:, j % Cw] for j < W (W = Cw or 2 Cw; the other columns of y are not touched).  coord
+    [N, 3] fp32 with any row stride (the [:, :3] view of pc_fts at level 0), cproj = coords_proj.weight [Cw, 3] (model.py:484-495)."""
+    assert not _capi.BF16, "the coordinate term of the attention runs with fp32 activation storage"
+    call("lotus_coord_add_fwd", y, y.stride(0), W, Cw, coord, coord.stride(0), cproj, y.shape[0])
+
+
+_COORD_WS_SLOT = 7  # workspace slot of the coordinate term's weight-gradient partials (main stream)
+
+
+def coord_add_wgrad(dy, W, Cw, coord):
+    """-> d cproj [Cw, 3] = sum over the rows of (dy[:, :Cw] (+ dy[:, Cw:2 Cw] when W = 2 Cw))^T coord, on the calling stream."""
+    assert not _capi.BF16, "the coordinate term of the attention runs with fp32 activation storage"
+    n = dy.shape[0]
+    dP = torch.empty(Cw, 3, dtype=torch.float32, device=dy.device)
+    ws = WS.get(query("lotus_coord_add_workspace", n, W, Cw), dy.device, slot=_COORD_WS_SLOT)
+    call("lotus_coord_add_wgrad", dy, dy.stride(0), W, Cw, coord, coord.stride(0), n, dP, ws, ws.numel())
+    return dP
+
+
+def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, attn_p, dpath, coord=None, cproj=None, cmode=None):
     """n = norm(x) -> (y, qkv, att, lse), y = x + DropPath(drop(proj(PatchAttention(qkv(n))))); qn / kn = (weight, bias), or
-    both None for attention without q/k normalisation."""
+    both None for attention without q/k normalisation.  coord / cproj / cmode: add_coords_in_attn (model.py:484-495) — 'qkv' adds
+    coord cproj^T to `n` IN PLACE before the qkv product (the caller saves that n: it is what the product's weight gradient reads),
+    'qk' adds it to the q and the k columns of the product."""
     N, C = x.shape
+    if cmode == "qkv":
+        coord_add_fwd(n, C, C, coord, cproj)
     qkv, _ = linear_fwd(n, wqkv, bqkv)
+    if cmode == "qk":
+        coord_add_fwd(qkv, 2 * C, C, coord, cproj)
     att = torch.empty(N, C, dtype=x.dtype, device=x.device)
     lse = torch.empty(lvl.npad, H, dtype=torch.float32, device=x.device)
     attention_fwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles,
@@ -1282,9 +1308,9 @@ def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, 
     return y, qkv, att, lse
 
 
-def selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, qn, kn, wp, lvl, H, p, seed, attn_p, dpath, hand):
-    """-> (dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp); `hand`: the hand-over that may hold dy pre-masked (or None).
-    gq, bq, gk, bk are None when qn = kn = None."""
+def selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, qn, kn, wp, lvl, H, p, seed, attn_p, dpath, hand, coord=None, cmode=None):
+    """-> (dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, dcproj); `hand`: the hand-over that may hold dy pre-masked (or None).
+    gq, bq, gk, bk are None when qn = kn = None; dcproj is None without the coordinate term (cmode None)."""
     N, C = n.shape
     dyb = drop_path(dy, None, dpath, mix_seed(seed, 5)) if dpath > 0.0 else dy
     dz = _masked(dyb, p, seed, hand)
@@ -1299,8 +1325,11 @@ def selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, qn, kn, wp, lvl, H, p, seed,
                                    datt, lse, dqkv, 3 * C, 0, dqkv, 3 * C, C, 2 * C, 0, 0, H, C // H, attn_p, mix_seed(seed, 1),
                                    lvl.kext, lvl.ext_pos, lvl.n_extra, extra)
     dwqkv, dbqkv = linear_wgrad(dqkv, n)
+    dcproj = coord_add_wgrad(dqkv, 2 * C, C, coord) if cmode == "qk" else None
     dn = linear_dgrad(dqkv, wqkv)
-    return dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp
+    if cmode == "qkv":
+        dcproj = coord_add_wgrad(dn, C, C, coord)
+    return dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, dcproj
 
 
 def ffn_branch_fwd(n, x, w1, b1, w2, b2, drop_p, seed, dpath):
@@ -1489,8 +1518,10 @@ class SelfAttnFn(torch.autograd.Function):
 
     @_fwd
     def forward(ctx, x, g, b, wqkv, bqkv, qnw, qnb, knw, knb, wp, bp, lvl, H, drop_p, seed, attn_p=0.0, hand_in=None, dpath=0.0,
-                mod=None, bank=None, j=0):
-        """qnw = qnb = knw = knb = None: a block without q_norm / k_norm (qk_norm False)."""
+                mod=None, bank=None, j=0, coord=None, cproj=None, cmode=None):
+        """qnw = qnb = knw = knb = None: a block without q_norm / k_norm (qk_norm False).  coord / cproj / cmode: the level's
+        float coordinates [N, 3], coords_proj.weight [C, 3] and 'qk' | 'qkv' (add_coords_in_attn, model.py:484-495); the node then
+        runs per launch, fp32 storage."""
         N, C = x.shape
         d = C // H
         ctx.meta = (lvl, H, d, drop_p, seed, attn_p)
@@ -1501,7 +1532,14 @@ class SelfAttnFn(torch.autograd.Function):
         if hand_in is not None:
             hand_in.arm(drop_p, seed)
         ctx.site = (bank, j)
-        ctx.comp = mod is None and qnw is not None and composites_enabled() and C % 4 == 0 and dpath == 0.0
+        ctx.comp = coord is None and mod is None and qnw is not None and composites_enabled() and C % 4 == 0 and dpath == 0.0
+        ctx.cmode = None
+        if coord is not None:
+            if cmode not in ("qk", "qkv") or cproj is None:
+                raise ValueError(f"SelfAttnFn: coord needs cproj and cmode 'qk' | 'qkv', got cmode={cmode!r}")
+            if _capi.BF16:
+                raise NotImplementedError("add_coords_in_attn runs with fp32 activation storage only")
+            ctx.cmode = cmode
         (wqkvk, wpk), pc = _wk(wqkv, wp)
         ctx.wk, ctx.pc = (wqkvk, wpk), pc
         if ctx.comp:
@@ -1516,7 +1554,9 @@ class SelfAttnFn(torch.autograd.Function):
             return y
         n, mean, rstd = ln_fwd(x, g, b, mod=mod, lvl=lvl)
         qn, kn = ((qnw, qnb), (knw, knb)) if qnw is not None else (None, None)
-        y, qkv, att, lse = selfattn_branch_fwd(n, x, wqkvk, bqkv, qn, kn, wpk, bp, lvl, H, drop_p, seed, attn_p, dpath)
+        y, qkv, att, lse = selfattn_branch_fwd(n, x, wqkvk, bqkv, qn, kn, wpk, bp, lvl, H, drop_p, seed, attn_p, dpath,
+                                               coord, cproj, ctx.cmode)
+        ctx.coord = coord  # (no gradient flows to it: kept as an attribute, like the level's tables)
         ctx.save_for_backward(x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd, b, mod)
         return y
 
@@ -1536,14 +1576,15 @@ class SelfAttnFn(torch.autograd.Function):
                            lvl.owner, lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, lvl.kext, lvl.ext_pos, lvl.n_extra, lvl.npad,
                            N, C, H, float(d ** -0.5), float(p), int(seed), float(attn_p), mix_seed(seed, 1), ctx.pc, wsm, wsm.numel(),
                            wss, wss_bytes, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
-            return (dx,) + _grad_views(grads, "self", C, H) + (None,) * 10
+            return (dx,) + _grad_views(grads, "self", C, H) + (None,) * 13
         x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd, b, mod = ctx.saved_tensors
         qn, kn = ((qnw, qnb), (knw, knb)) if qnw is not None else (None, None)
-        dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp = selfattn_branch_bwd(dy, n, qkv, att, lse, ctx.wk[0], qn, kn, ctx.wk[1], lvl, H,
-                                                                         p, seed, attn_p, ctx.dpath, ctx.hand_in)
+        dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, dcproj = selfattn_branch_bwd(dy, n, qkv, att, lse, ctx.wk[0], qn, kn, ctx.wk[1],
+                                                                                 lvl, H, p, seed, attn_p, ctx.dpath, ctx.hand_in,
+                                                                                 ctx.coord, ctx.cmode)
         dmod = _dmod(mod, ctx.site)
         dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy, b=b, mod=mod, dmod=dmod, lvl=lvl)
-        return (dx, dg, db, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp) + (None,) * 7 + (dmod, None, None)
+        return (dx, dg, db, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp) + (None,) * 7 + (dmod, None, None, None, dcproj, None)
 
 
 class CrossAttnFn(torch.autograd.Function):

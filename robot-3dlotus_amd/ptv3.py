@@ -40,13 +40,17 @@ def _bn(c):
 
 
 class _Attn(nn.Module):
-    def __init__(self, c, h, qk_norm=True):
+    def __init__(self, c, h, qk_norm=True, coords=False):
+        """coords: False, or add_coords_in_attn 'qk' | 'qkv' (model.py:396-398, 484-495)."""
         super().__init__()
         self.qkv = nn.Linear(c, 3 * c)
         self.proj = nn.Linear(c, c)
         # qk_norm False: nn.Identity, as the reference registers (model.py:393-394) — same module names, no state entries
         self.q_norm = nn.LayerNorm(c // h, eps=1e-6) if qk_norm else nn.Identity()
         self.k_norm = nn.LayerNorm(c // h, eps=1e-6) if qk_norm else nn.Identity()
+        self.coords_mode = coords or None
+        if coords:  # registered after k_norm, as the reference does: the state-dict key order is its own
+            self.coords_proj = nn.Linear(3, c, bias=False)
 
 
 class _CrossAttn(nn.Module):
@@ -98,8 +102,13 @@ class Block(nn.Module):
         handed = qk and mods is None
         h_attn, h_mlp = (ops.Handoff(), ops.Handoff()) if handed else (None, None)
         gb, ada = site(self.norm1[0])
-        x = ops.SelfAttnFn.apply(x, *gb, a.qkv.weight, a.qkv.bias, *qkn, a.proj.weight, a.proj.bias, lvl, self.num_heads,
-                                 drop_p, seed, attn_p, h_attn, dpath, *ada)
+        if a.coords_mode is None:
+            x = ops.SelfAttnFn.apply(x, *gb, a.qkv.weight, a.qkv.bias, *qkn, a.proj.weight, a.proj.bias, lvl, self.num_heads,
+                                     drop_p, seed, attn_p, h_attn, dpath, *ada)
+        else:  # add_coords_in_attn: the level's float coordinates enter the attention's input (the node runs per launch)
+            x = ops.SelfAttnFn.apply(x, *gb, a.qkv.weight, a.qkv.bias, *qkn, a.proj.weight, a.proj.bias, lvl, self.num_heads,
+                                     drop_p, seed, attn_p, h_attn, dpath, *(ada or (None, None, 0)), lvl.coord,
+                                     a.coords_proj.weight, a.coords_mode)
         gb, ada = site(self.norm2[0])
         x = ops.FfnFn.apply(x, *gb, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, drop_p, ops.mix_seed(seed, 2), h_mlp,
                             h_attn, dpath, lvl, *ada)
@@ -185,6 +194,7 @@ class PointTransformerV3CA(nn.Module):
     block(s) at depth i of a stage"."""
     block_cls = Block  # the type _blocks / _block_level index
     plain_attention = False  # whether the class runs qk_norm=False (attention without q/k LayerNorm): the AdaNorm backbone only
+    coord_attention = False  # whether the class runs add_coords_in_attn 'qk' / 'qkv': the AdaNorm and the Concat backbone
 
     def __init__(self, in_channels=6, order=("z", "z-trans", "hilbert", "hilbert-trans"), stride=(2, 2, 2, 2),
                  enc_depths=(2, 2, 2, 6, 2), enc_channels=(32, 64, 128, 256, 512), enc_num_head=(2, 4, 8, 16, 32),
@@ -197,11 +207,14 @@ class PointTransformerV3CA(nn.Module):
                  pdnorm_conditions=("ScanNet", "S3DIS", "Structured3D"), pdnorm_only_decoder=False,
                  add_coords_in_attn=False, scaled_cosine_attn=False):
         super().__init__()
+        if add_coords_in_attn not in (False, None, "none", "qk", "qkv"):
+            raise ValueError(f"add_coords_in_attn={add_coords_in_attn!r}: one of 'none', 'qk', 'qkv' (model.py:484-495)")
+        self.add_coords = add_coords_in_attn if add_coords_in_attn in ("qk", "qkv") else False
         pd = self._pdnorm_unsupported(pdnorm_bn, pdnorm_ln, pdnorm_decouple, pdnorm_adaptive, pdnorm_affine, pdnorm_only_decoder)
         unsupported = dict(**pd, enable_rpe=enable_rpe, cls_mode=cls_mode,
                            scaled_cosine_attn=scaled_cosine_attn, not_flash=not enable_flash, not_qk_norm=not qk_norm and not self.plain_attention,
                            not_pre_norm=not pre_norm, no_qkv_bias=not qkv_bias, qk_scale=qk_scale is not None,
-                           add_coords=add_coords_in_attn not in (False, "none", None),
+                           add_coords=bool(self.add_coords) and not self.coord_attention,
                            depth_lt_1=any(d < 1 for d in list(enc_depths) + list(dec_depths)),
                            stride_ne_2=any(s != 2 for s in stride),
                            patch_ne_128=any(p > 128 for p in list(enc_patch_size) + list(dec_patch_size)))

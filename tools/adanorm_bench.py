@@ -3,12 +3,18 @@
     python tools/adanorm_bench.py [--steps 20] [--windows 5] [--out path.json]
     python tools/adanorm_bench.py --rehearsal [--steps 20] [--windows 5] [--out path.json]
     python tools/adanorm_bench.py --presets adanorm_v1,adanorm_v1_plain [--steps 20] [--windows 5] [--out path.json]
+    python tools/adanorm_bench.py --presets adanorm_yaml --add-coords qk [--steps 20] [--windows 5] [--out path.json]
 
 The two models alternate window by window in one process (same batch, same warm-up); each reports the median of its
 windows.  The AdaNorm batch carries one instruction token per cloud (txt_reduce 'mean', instr_embed_type 'last').
 
 --presets A,B: two presets of config.preset() instead (built through policy.MODEL_FACTORY), e.g. the AdaNorm policy with and
 without q/k LayerNorm in the patch attention; reports both medians, the window rates, B over A and the library hash.
+
+--add-coords {none,qk,qkv}: ptv3_config.add_coords_in_attn of the presets.  With ONE preset name the preset as it is (A) alternates
+with the preset under that mode (B, reported as "<name>+<mode>"): the cost of the coordinate term of the patch attention; with two
+names the mode is set in both.  A preset with 6 input channels / 'euler' rotations (the shipped YAML) gets the batch cut and
+labelled for it.
 
 --rehearsal: the one-rank RCCL rehearsal of the data-parallel AdaNorm step (LOTUS_FORCE_COLLECTIVES=1, nccl backend: every
 collective of the step goes through the real library on one device) against the plain AdaNorm step, alternating windows in one
@@ -47,27 +53,45 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--rehearsal", action="store_true", help="one-rank RCCL data-parallel step against the plain AdaNorm step")
     ap.add_argument("--presets", default=None, help="A,B: two presets of config.preset() to alternate instead of AdaNorm / CA")
+    ap.add_argument("--add-coords", default="none", choices=("none", "qk", "qkv"),
+                    help="add_coords_in_attn of the presets; with one preset name: the preset as it is against the preset with it")
     a = ap.parse_args()
     if a.rehearsal:
         return rehearsal(a)
     torch.manual_seed(0)
     batch = au.last_token_batch(synth.augment_clouds(synth.synth_batch(16, 4096, seed=0), seed=1))
+    batches = {}
     if a.presets:
         from robot_3dlotus_amd.policy import MODEL_FACTORY
 
         names = a.presets.split(",")
-        assert len(names) == 2 and names[0] != names[1], "--presets takes two different preset names: A,B"
+        if a.add_coords != "none" and len(names) == 1:
+            variants = [(names[0], "none"), (f"{names[0]}+{a.add_coords}", a.add_coords)]
+        else:
+            assert len(names) == 2 and names[0] != names[1], "--presets takes two different preset names: A,B"
+            variants = [(n, a.add_coords) for n in names]
         models = {}
-        for n in names:
-            cfg = lcfg.preset(n)
-            models[n] = MODEL_FACTORY[cfg.model_class](cfg).cuda().train()
+        for label, mode in variants:
+            cfg = lcfg.preset(label.split("+")[0])
+            if a.add_coords != "none":
+                cfg.ptv3_config.add_coords_in_attn = mode
+            models[label] = MODEL_FACTORY[cfg.model_class](cfg).cuda().train()
+            if cfg.action_config.rot_pred_type == "euler" or cfg.ptv3_config.in_channels != batch["pc_fts"].shape[1]:
+                bb = au.last_token_batch(synth.augment_clouds(synth.synth_batch(16, 4096, seed=0, rot_type=cfg.action_config.rot_pred_type),
+                                                              seed=1))
+                bb["pc_fts"] = bb["pc_fts"][:, :cfg.ptv3_config.in_channels].contiguous()
+                batches[label] = _dev(bb)
     else:
+        assert a.add_coords == "none", "--add-coords goes with --presets"
         models = {"adanorm": SimplePolicyPTV3AdaNorm(lcfg.preset("adanorm_v1")).cuda().train(),
                   "ca": SimplePolicyPTV3CA(lcfg.preset("v1")).cuda().train()}
     b = _dev(batch)
+    for k in models:
+        batches.setdefault(k, b)
+    batch_of = {id(m): batches[k] for k, m in models.items()}
 
     def step(m):
-        _, losses = m(b, compute_loss=True, compute_final_action=False)
+        _, losses = m(batch_of[id(m)], compute_loss=True, compute_final_action=False)
         losses["total"].backward()
         for p in m.parameters():
             p.grad = None
