@@ -368,6 +368,9 @@ int lotus_attention_bwd(const lotus_act_t* q, long q_ld, int q_off, const lotus_
  *   family    1 attn_fwd_kernel (128 x 128 tile)       2 attn_bwd_kernel (tile, bf16 / bf16x3 operands)
  *             3 attn_bwd2_kernel (tile, exact fp32)    4 xq_fwd / xq_bwd_kernel (one lane per query, keys in LDS)
  *             5 xq2_fwd / xq2_bwd_kernel (one lane per query, key tile in registers)
+ *             6 attn_rpe_fwd_kernel, 7 attn_rpe_bwd_kernel (lotus_attention_rpe_fwd / _bwd: the exact-fp32 tile kernels with the
+ *               relative-position term; precision 0, targ 0, 256 threads, lds_bytes 57 216 forward and 74 112 + 1 536 (2 bnd + 1)
+ *               backward; tail bit 2 = attn_rpe_merge_kernel, always set by family 7)
  *   direction 0 forward, 1 backward
  *   targ      the kernel's template argument: head width D = 32 | 24 | 16 (4), NW = 4 (5), 0 for the tile families
  *   precision the operand mode of the kernel that runs: 0 exact fp32, 1 bf16, 3 bf16x3 (families 3, 4, 5: always 0)
@@ -770,6 +773,46 @@ int lotus_coord_add_wgrad(const float* dy, long ld, int W, int Cw, const float* 
  * gradient, rows a thread sums in fp32 at a time, quad lanes and row lanes of its block (a range of at most row lanes x rows per
  * thread rows is one fp32 chunk per thread; the splits stop growing at 256)}.  Refuses what the entry points refuse. */
 int lotus_coord_add_plan(int n, int W, int Cw, int* out);
+
+/* ---- patch attention with the relative-position term, enable_rpe (fp32 only, no bf16 twin; csrc/attention_rpe.hip) --------------
+ * PointTransformerV3/model.py:307-326 (RPE), :400-408 and the non-flash branch of SerializedAttention.forward, :518-527: before the
+ * softmax the score of query row i and key row j of a patch, head h, gets
+ *     sum_{a in x, y, z} table[a (2 bnd + 1) + clamp(g_i[a] - g_j[a], -bnd, bnd) + bnd][h]
+ * added, NOT multiplied by `scale`.  grid: int32 [n][3], indexed by the row numbers qidx / kidx yield (the positions themselves
+ * when those are null); table: rpe.rpe_table, [3 (2 bnd + 1)][H]; bnd = pos_bnd.  The exact-fp32 128 x 128 tile kernels
+ * (families 1 / 3 of lotus_attention_last_route) with the term inside; q_len == k_len of a tile is not assumed.
+ *   lotus_attention_rpe_fwd:  the arguments of lotus_attention_fwd without precision and k_max, then grid, table, bnd.  out, lse,
+ *       the q/k-norm pointers (all four given or all four null) and the dropout on the probabilities (same mask function, same
+ *       element numbering: with a table of zeros and the same seed it computes what lotus_attention_fwd computes) as there.
+ *   lotus_attention_rpe_bwd:  the arguments of lotus_attention_bwd without atomic_out, precision and k_max (plain stores; the
+ *       gradients of borrowed rows go to dkv_extra), then grid, table, bnd, dtable and the workspace.
+ *       dtable[r][h] = sum over every patch and every (query, key) pair whose clamped offset selects row r on its axis of
+ *       G = P o (dP - delta), the gradient of the pre-softmax score (dropout mask applied as for dS; NOT times `scale`).  WRITTEN,
+ *       not accumulated; rows no pair selects are exact zeros; nblocks == 0 writes zeros.  No atomics: per-key fp32 bins in LDS
+ *       filled in program order, summed over a block's keys and then over the blocks in ascending order in float64 — reruns are
+ *       bit-identical.  workspace: lotus_attention_rpe_bwd_workspace(nblocks, H, bnd) bytes, 8-byte aligned (the norm's partials
+ *       and one float64 row of 3 (2 bnd + 1) per (block, head)).
+ * LOTUS_E_ARG before any launch, with a message: a null pointer among q, kv, tiles, out (backward: blocks, out, dout, lse, dq,
+ * dkv, dtable), grid or table null (a table without grid says so), H <= 0, d not a multiple of 4 in [4, 32], bnd < 0,
+ * bnd > 15 (the pos_bnd of a 128-row patch: the head's table column and the bins are held in LDS), drop_p outside [0, 1), some but
+ * not all of the norm pointers, a null norm gradient with the norm, ntiles / nblocks < 0, a short or misaligned workspace, borrowed
+ * rows without dkv_extra / ext_pos / kidx or with k | v column blocks that are not adjacent.  A tile's q_len and k_len must be
+ * <= 128 (the caller's contract, as at lotus_attention_fwd).  A refused call leaves the route record as it was. */
+int lotus_attention_rpe_fwd(const float* q, long q_ld, int q_off, const float* kv, long kv_ld, int k_off, int v_off,
+                            const int* qidx, const int* kidx, const int* owner, const int* tiles, int ntiles,
+                            const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b, float* out,
+                            long out_ld, float* lse, int H, int d, float scale, float eps, float drop_p,
+                            unsigned long long drop_seed, const int* grid, const float* table, int bnd, void* stream);
+size_t lotus_attention_rpe_bwd_workspace(int nblocks, int H, int bnd);
+int lotus_attention_rpe_bwd(const float* q, long q_ld, int q_off, const float* kv, long kv_ld, int k_off, int v_off,
+                            const int* qidx, const int* kidx, const int* owner, const int* tiles, const int* blocks,
+                            int nblocks, const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b,
+                            const float* out, const float* dout, long out_ld, const float* lse, float* dq, long dq_ld,
+                            int dq_off, float* dkv, long dkv_ld, int dk_off, int dv_off, long dkv_part_stride,
+                            const int* kext, const int* ext_pos, int n_extra, float* dkv_extra, float* dqn_w, float* dqn_b,
+                            float* dkn_w, float* dkn_b, int accumulate, int H, int d, float scale, float eps, float drop_p,
+                            unsigned long long drop_seed, const int* grid, const float* table, int bnd, float* dtable,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -114,12 +114,12 @@ class AdaBlock(nn.Module):
     qk_norm is False: the patch attention then runs without them).  Not a ptv3.Block (whose constructor builds the plain norms),
     but run by its walker."""
 
-    def __init__(self, c, h, mlp_ratio, ctx, qk_norm=True, coords=False):
+    def __init__(self, c, h, mlp_ratio, ctx, qk_norm=True, coords=False, rpe_patch=None):
         super().__init__()
         self.num_heads = h
         self.cpe = nn.Sequential(SubMConv3d(c, c, 3, bias=True), nn.Linear(c, c), _pd_ln(c, ctx))
         self.norm1 = nn.Sequential(_pd_ln(c, ctx))
-        self.attn = _Attn(c, h, qk_norm, coords)
+        self.attn = _Attn(c, h, qk_norm, coords, rpe_patch)
         self.norm2 = nn.Sequential(_pd_ln(c, ctx))
         self.mlp = nn.Sequential(_MLP(c, int(c * mlp_ratio)))
 
@@ -173,6 +173,7 @@ class PointTransformerV3AdaNorm(PointTransformerV3CA):
     block_cls = AdaBlock
     plain_attention = True
     coord_attention = True
+    dense_attention = True
 
     def __init__(self, *args, pdnorm_bn=True, pdnorm_ln=True, pdnorm_decouple=False, pdnorm_adaptive=True, **kw):
         super().__init__(*args, pdnorm_bn=pdnorm_bn, pdnorm_ln=pdnorm_ln, pdnorm_decouple=pdnorm_decouple,
@@ -198,7 +199,8 @@ class PointTransformerV3AdaNorm(PointTransformerV3CA):
         return _AdaUp(cin, cskip, cout, self.context_channels)
 
     def _add_depth(self, stage, i, c, h, mlp_ratio):
-        stage.add_module(f"block{i}", AdaBlock(c, h, mlp_ratio, self.context_channels, self.qk_norm, self.add_coords))
+        stage.add_module(f"block{i}", AdaBlock(c, h, mlp_ratio, self.context_channels, self.qk_norm, self.add_coords,
+                                                   self.rpe_patch))
 
     def _index_sites(self):
         self._pdnorms = [m for m in self.modules() if isinstance(m, PDNorm)]  # slice j of the modulation bank = norm j

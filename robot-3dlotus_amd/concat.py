@@ -95,10 +95,10 @@ class CtxStemFn(torch.autograd.Function):
 class PlainBlock(Block):
     """model.py:586-680; qk_norm False registers attn.q_norm / k_norm as nn.Identity (model.py:393-394): no state entries."""
 
-    def __init__(self, c, h, mlp_ratio, qk_norm=True, coords=False):
+    def __init__(self, c, h, mlp_ratio, qk_norm=True, coords=False, rpe_patch=None):
         super().__init__(c, h, mlp_ratio)
-        if not qk_norm or coords:
-            self.attn = _Attn(c, h, qk_norm, coords)
+        if not qk_norm or coords or rpe_patch:
+            self.attn = _Attn(c, h, qk_norm, coords, rpe_patch)
 
 
 class PointTransformerV3Plain(PointTransformerV3CA):
@@ -107,6 +107,7 @@ class PointTransformerV3Plain(PointTransformerV3CA):
     in_channels = c_pc + pdnorm_context_channels is the width of embedding.stem.conv.weight, as in the reference."""
     plain_attention = True
     coord_attention = True
+    dense_attention = True
 
     def __init__(self, in_channels=6, *args, **kw):
         super().__init__(in_channels, *args, **kw)
@@ -134,7 +135,7 @@ class PointTransformerV3Plain(PointTransformerV3CA):
         return pdnorm_context_channels
 
     def _add_depth(self, stage, i, c, h, mlp_ratio):
-        stage.add_module(f"block{i}", PlainBlock(c, h, mlp_ratio, self.qk_norm, self.add_coords))
+        stage.add_module(f"block{i}", PlainBlock(c, h, mlp_ratio, self.qk_norm, self.add_coords, self.rpe_patch))
 
     def _index_sites(self):
         pass

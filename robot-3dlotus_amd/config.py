@@ -214,6 +214,21 @@ CONCAT_OVERRIDES.update({"concat_tiny_qk": CONCAT_OVERRIDES["concat_tiny"] + _co
 MP_ADA_OVERRIDES["mp_ada_tiny_qkv"] = MP_ADA_OVERRIDES["mp_ada_tiny"] + _coords("qkv")
 
 
+# enable_flash False / enable_rpe True (simple_policy_ptv3.yaml:117-120, motion_planner_ptv3.yaml:127-130; PointTransformerV3/
+# model.py:307-326, :469-472, :499-527) on the AdaNorm and the Concat backbone: the non-flash patching (per-level patch size =
+# min(patch size, fewest points of a cloud)) alone ('adanorm_tiny_dense') and with the relative-position term.  'adanorm_yaml_rpe'
+# is the shipped YAML with those two keys flipped (qk_norm False); adanorm_tiny_plain_rpe and mp_ada_tiny_rpe have qk_norm False too,
+# adanorm_tiny_rpe and concat_tiny_rpe qk_norm True.
+DENSE_ATTN = ["ptv3_config.enable_flash", "False"]
+RPE_ATTN = DENSE_ATTN + ["ptv3_config.enable_rpe", "True"]
+ADANORM_OVERRIDES.update({"adanorm_tiny_dense": ADANORM_OVERRIDES["adanorm_tiny"] + DENSE_ATTN,
+                          "adanorm_tiny_rpe": ADANORM_OVERRIDES["adanorm_tiny"] + RPE_ATTN,
+                          "adanorm_tiny_plain_rpe": ADANORM_OVERRIDES["adanorm_tiny_plain"] + RPE_ATTN,
+                          "adanorm_yaml_rpe": RPE_ATTN})
+CONCAT_OVERRIDES["concat_tiny_rpe"] = CONCAT_OVERRIDES["concat_tiny"] + RPE_ATTN
+MP_ADA_OVERRIDES["mp_ada_tiny_rpe"] = MP_ADA_OVERRIDES["mp_ada_tiny"] + RPE_ATTN
+
+
 def preset(name="v1"):
     """'v1' / 'tiny': 3D-LOTUS policy; 'peract': the RLBench-18task (PerAct) variant of BASELINE configs[4] (same network;
     its bf16 compute mode is ops.set_gemm_precision("bf16")); 'mp' / 'mp_tiny': 3D-LOTUS++ motion planner (configs[3]);
@@ -224,7 +239,9 @@ def preset(name="v1"):
     'mp_yaml': motion_planner_ptv3.yaml as shipped (MotionPlannerPTV3AdaNorm, soft trajectory head); 'mp_ada_tiny': its tiny width;
     'concat_yaml' / 'concat_tiny': SimplePolicyPTV3Concat on the YAML's networks (in_channels 262) / the tiny ones (263);
     'adanorm_tiny_qk' / 'adanorm_tiny_qkv' / 'adanorm_yaml_qk' / 'concat_tiny_qk' / 'concat_tiny_qkv' / 'mp_ada_tiny_qkv': their
-    base preset with add_coords_in_attn 'qk' / 'qkv' (adanorm_tiny_qk on adanorm_tiny_plain: qk_norm False)."""
+    base preset with add_coords_in_attn 'qk' / 'qkv' (adanorm_tiny_qk on adanorm_tiny_plain: qk_norm False);
+    'adanorm_tiny_dense': adanorm_tiny with enable_flash False; 'adanorm_tiny_rpe' / 'adanorm_tiny_plain_rpe' / 'concat_tiny_rpe' /
+    'mp_ada_tiny_rpe' / 'adanorm_yaml_rpe': their base preset with enable_flash False and enable_rpe True."""
     if name in ("mp", "mp_tiny", "mp_tinyctx"):
         model = copy.deepcopy(_YAML_MODEL)
         model["model_class"] = _YAML_MP_DELTA["model_class"]

@@ -55,7 +55,7 @@ class Level:
     __slots__ = ("n", "counts", "off", "off_host", "grid", "batch", "code", "order", "inverse", "depth", "nbr27",
                  "nbr125", "gidx", "owner", "kext", "ext_pos", "n_extra", "npad", "self_tiles", "self_blocks", "n_self_tiles", "ca_tiles",
                  "ca_blocks", "n_ca_tiles", "n_ca_blocks", "ca_groups", "cluster", "seg_start", "members",
-                 "coord", "parent", "n_dup", "patch", "_views", "ca_kmax", "_patch_args", "tap_plan")
+                 "coord", "parent", "n_dup", "patch", "_views", "ca_kmax", "_patch_args", "tap_plan", "K")
 
     def for_order(self, k):
         """The level as the k-th block of a stage sees it: `Block(order_index = i % len(order))` attends along curve slot k
@@ -91,8 +91,13 @@ def draw_order_perms(n_levels, shuffle=True):
 
 
 class FrontEnd:
-    def __init__(self, n_levels, patch_size=128, grid_size=0.01, orders=ORDERS, n_patch_orders=1, conv_widths=None):
+    def __init__(self, n_levels, patch_size=128, grid_size=0.01, orders=ORDERS, n_patch_orders=1, conv_widths=None,
+                 min_count_patches=False):
+        """min_count_patches: the patching of the reference's non-flash attention (enable_flash False, model.py:469-472) — level s
+        is patched at K_s = min(patch_size, fewest points any cloud has at level s) instead of patch_size, so every patch has
+        exactly K_s rows.  The counts are on the host when the plans are made: no extra copy, no extra kernel."""
         self.n_levels = n_levels
+        self.min_count_patches = bool(min_count_patches)
         # widest 3^3 convolution of every level (None: unknown): levels with few rows and wide layers get a tap plan
         # (lotus_fe_tap_plan) for the tap-grouped convolution path, csrc/conv.hip
         self.conv_widths = list(conv_widths) if conv_widths is not None else None
@@ -102,6 +107,36 @@ class FrontEnd:
         self.order_ids = [ORDERS.index(o) for o in orders]
         assert len(self.order_ids) == 4, "the HIP front-end is built for the 4-curve configuration"
         self.depth_bound = 16  # tightened to the observed depth after the first batch
+
+    def level_patch_size(self, counts):
+        """Patch size of a level whose clouds have `counts` points: patch_size, or with min_count_patches the smaller of it and
+        the fewest points of a cloud (at least 1)."""
+        if not self.min_count_patches or len(counts) == 0:
+            return self.K
+        return max(1, min(self.K, int(min(counts))))
+
+    def patch_plan(self, counts):
+        """Host plan of the patch attention of a level whose clouds have `counts` points (no device involved) -> (K, off [B + 1],
+        offp [B + 1], tiles [nt][4] = q_start, q_len, k_start, k_len, blocks [nt][6] = first_tile, n_tiles, tile_step, part_slot,
+        k_start, k_len), int64.  K = level_patch_size(counts); a cloud longer than K is padded to a multiple of K (its tail patch
+        borrows the rows before it, get_padding_and_inverse, model.py:410-466), a shorter one is one tile of its own length."""
+        c = np.asarray(counts, dtype=np.int64)
+        K = self.level_patch_size(c)
+        ar_b = np.arange(len(c))
+        # vectorised over the clouds (a Python loop per cloud and tile cost 0.7 ms of host time per step)
+        off = np.concatenate([[0], np.cumsum(c)])
+        cpad = np.where(c > K, (c + K - 1) // K * K, c)
+        offp = np.concatenate([[0], np.cumsum(cpad)])
+        # self-attention patches: one tile per patch of <= K serialised points (a short cloud is one tile)
+        nseg = np.where(c == 0, 0, np.where(c <= K, 1, cpad // K))
+        nt_self = int(nseg.sum())
+        cb = np.repeat(ar_b, nseg)
+        within = np.arange(nt_self) - np.repeat(np.cumsum(nseg) - nseg, nseg)
+        st = offp[cb] + within * K
+        ln = np.where(c[cb] <= K, c[cb], K)
+        tiles = np.stack([st, ln, st, ln], 1)
+        blocks = np.stack([np.arange(nt_self), np.ones(nt_self, np.int64), np.ones(nt_self, np.int64), np.zeros(nt_self, np.int64), st, ln], 1)
+        return K, off, offp, tiles, blocks
 
     @torch.no_grad()
     def build(self, pc_fts, counts, ctx_counts, perms, need_coord=False):
@@ -238,7 +273,6 @@ class FrontEnd:
         # ---- exact-size tables per level
         levels = []
         host_tabs, host_slices = [], []
-        K = self.K
 
         def push(arr):
             arr = np.ascontiguousarray(arr, dtype=np.int32).reshape(-1)
@@ -251,20 +285,9 @@ class FrontEnd:
         plans = []
         ar_b = np.arange(B)
         for s in range(Lv):
-            # vectorised over the clouds (a Python loop per cloud and tile cost 0.7 ms of host time per step)
             c = cnt_h[s].astype(np.int64)
-            off = np.concatenate([[0], np.cumsum(c)])
-            cpad = np.where(c > K, (c + K - 1) // K * K, c)
-            offp = np.concatenate([[0], np.cumsum(cpad)])
-            # self-attention patches: one tile per patch of <= K serialised points (a short cloud is one tile)
-            nseg = np.where(c == 0, 0, np.where(c <= K, 1, cpad // K))
-            nt_self = int(nseg.sum())
-            cb = np.repeat(ar_b, nseg)
-            within = np.arange(nt_self) - np.repeat(np.cumsum(nseg) - nseg, nseg)
-            st = offp[cb] + within * K
-            ln = np.where(c[cb] <= K, c[cb], K)
-            tiles = np.stack([st, ln, st, ln], 1)
-            blocks = np.stack([np.arange(nt_self), np.ones(nt_self, np.int64), np.ones(nt_self, np.int64), np.zeros(nt_self, np.int64), st, ln], 1)
+            K, off, offp, tiles, blocks = self.patch_plan(c)
+            nt_self = len(tiles)
             # cross-attention: 128-row tiles of a cloud's points x that cloud's instruction tokens; backward blocks = G
             # interleaved tile groups per cloud (one key-side partial slot each)
             nt = (c + 127) // 128
@@ -280,7 +303,7 @@ class FrontEnd:
             plans.append(dict(off=push(off), offp=push(offp), tiles=push(tiles), blocks=push(blocks),
                               ca_tiles=push(ca_tiles), ca_blocks=push(ca_blocks), n_tiles=nt_self,
                               n_ca_tiles=n_ca, n_ca_blocks=B * G, G=G, npad=int(offp[-1]),
-                              off_host=off))
+                              off_host=off, K=K))
         ntab = sum(a.size for a in host_tabs)
         tabs_h = torch.empty(ntab, dtype=torch.int32, pin_memory=True)  # pinned: the upload must not drain the queue
         np.concatenate(host_tabs, out=tabs_h.numpy())
@@ -304,7 +327,7 @@ class FrontEnd:
     def _finish_tables(self, pend, tabs_h, plans, ns, cnt_h, depth0, meta_h, ctx_counts, need_coord, made, ws_slot):
         pc_fts, counts, raw = pend["pc_fts"], pend["counts"], pend["raw"]
         dev = pc_fts.device
-        B, Lv, K = len(counts), self.n_levels, self.K
+        B, Lv = len(counts), self.n_levels
         i32 = dict(dtype=torch.int32, device=dev)
         levels = []
 
@@ -354,7 +377,8 @@ class FrontEnd:
             if s == 0:
                 lv.nbr125 = empty(125, n)
                 call("lotus_fe_neighbours", lv.grid, lv.batch, n, 5, lv.nbr125, ws_n, ws_n.numel())
-            lv.npad = pl["npad"]
+            lv.npad, lv.K = pl["npad"], pl["K"]
+            K = lv.K
             lv.gidx = empty(lv.npad)
             lv.owner = empty(lv.npad)
             lv.kext = empty(lv.npad)

@@ -322,6 +322,11 @@ class MotionPlannerPTV3AdaNorm(MotionPlannerPTV3CA):
             if mode != "fp32":  # the patch attention without q/k LayerNorm exists as exact-fp32 kernels only
                 raise NotImplementedError(f"MotionPlannerPTV3AdaNorm with qk_norm=False is built for gemm_precision None / 'fp32' "
                                           f"only, got {mode!r}")
+        if self.ptv3_model.enable_rpe:
+            mode = self.gemm_precision or ops.get_gemm_precision()
+            if mode != "fp32":  # the patch attention with the relative-position term exists as exact-fp32 kernels only
+                raise NotImplementedError(f"MotionPlannerPTV3AdaNorm with enable_rpe=True is built for gemm_precision None / 'fp32' "
+                                          f"only, got {mode!r}")
         return super().forward(batch, compute_loss, **kwargs)
 
     @property

@@ -61,13 +61,14 @@ def last_conv_route():
 
 AttnRoute = collections.namedtuple("AttnRoute", "family direction targ precision norm threads lds_bytes tail")
 ATTN_FWD, ATTN_BWD, ATTN_BWD2, ATTN_XQ, ATTN_XQ2 = range(1, 6)
+ATTN_RPE_FWD, ATTN_RPE_BWD = 6, 7  # lotus_attention_rpe_fwd / _bwd (csrc/attn_route.h)
 
 
 def last_attn_route():
     """The kernel this thread's last attention launch was given to (lotus_attention_last_route; fields in include/lotus_hip.h):
     family 1 tile forward, 2 tile backward on bf16 / bf16x3 operands, 3 tile backward in fp32, 4 / 5 one lane per query (keys in
-    LDS / in registers); direction 0 fwd / 1 bwd; template argument; operand precision; with the q/k norm; threads; dynamic LDS
-    bytes; tail (bit 0 fix-up, bit 1 norm-gradient reduction follow).  Set when the kernel is chosen, so it is there after a
+    LDS / in registers), 6 / 7 tile forward / backward with the relative-position term; direction 0 fwd / 1 bwd; template argument; operand precision; with the q/k norm; threads; dynamic LDS
+    bytes; tail (bit 0 fix-up, bit 1 norm-gradient reduction, bit 2 table-gradient merge follow).  Set when the kernel is chosen, so it is there after a
     launch that failed, too."""
     out = (ctypes.c_int * 8)()
     _capi.call_raw("lotus_attention_last_route", ctypes.addressof(out))
@@ -1117,6 +1118,45 @@ def attention_bwd(q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, ti
     return grads
 
 
+def rpe_bound(patch_size):
+    """pos_bnd of RPE for a configured patch size, by the reference's own expression (model.py:311): 15 at 128, since
+    512 ** (1 / 3) is 7.999..."""
+    return int((4 * patch_size) ** (1 / 3) * 2)
+
+
+def attention_rpe_fwd(q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, ntiles, qn, kn, out, lse, H, d, grid,
+                      table, bnd, drop_p=0.0, seed=0):
+    """attention_fwd with the relative-position term (model.py:307-326, :518-527): grid int32 [n, 3], table = rpe.rpe_table
+    [3 (2 bnd + 1), H].  Exact fp32, fp32 storage."""
+    assert not _capi.BF16, "the relative-position term of the attention runs with fp32 activation storage"
+    qn, kn = _qk_norms(qn, kn)
+    call("lotus_attention_rpe_fwd", q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, ntiles,
+         qn[0], qn[1], kn[0], kn[1], out, out.stride(0), lse, H, d, float(d ** -0.5), 1e-6, float(drop_p), int(seed),
+         grid, table, int(bnd))
+
+
+_RPE_WS_SLOT = 8  # workspace slot of the relative-position backward: norm partials and table-gradient partials (main stream)
+
+
+def attention_rpe_bwd(q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, blocks, nblocks, qn, kn, out,
+                      dout, lse, dq, dq_ld, dq_off, dkv, dkv_ld, dk_off, dv_off, part_stride, H, d, grid, table, bnd, drop_p=0.0,
+                      seed=0, kext=None, ext_pos=None, n_extra=0, dkv_extra=None):
+    """-> (the gradients of q_norm / k_norm: weight, bias, weight, bias — four None when qn = kn = None, dtable).  Plain stores;
+    the table gradient is written on the calling stream, without atomics."""
+    assert not _capi.BF16, "the relative-position term of the attention runs with fp32 activation storage"
+    dev = q.device
+    plain = qn is None and kn is None
+    qn, kn = _qk_norms(qn, kn)
+    grads = [None] * 4 if plain else [torch.empty(d, dtype=torch.float32, device=dev) for _ in range(4)]
+    dtable = torch.empty_like(table)
+    ws = WS.get(query("lotus_attention_rpe_bwd_workspace", nblocks, H, int(bnd)), dev, slot=_RPE_WS_SLOT)
+    call("lotus_attention_rpe_bwd", q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, blocks, nblocks,
+         qn[0], qn[1], kn[0], kn[1], out, dout, out.stride(0), lse, dq, dq_ld, dq_off, dkv, dkv_ld, dk_off, dv_off,
+         part_stride, kext, ext_pos, n_extra, dkv_extra, grads[0], grads[1], grads[2], grads[3], 0, H, d, float(d ** -0.5), 1e-6,
+         float(drop_p), int(seed), grid, table, int(bnd), dtable, ws, ws.numel())
+    return grads, dtable
+
+
 # ------------------------------------------------------------------------------------ composite fast path
 # One C call per sub-block direction (csrc/blocks.cpp) instead of one per launch: same entry points, same order, same
 # streams -> bit-identical results (tests/test_gpu_blocks.py), ~70 % less interpreter time inside the sub-blocks.  The
@@ -1285,11 +1325,13 @@ def coord_add_wgrad(dy, W, Cw, coord):
     return dP
 
 
-def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, attn_p, dpath, coord=None, cproj=None, cmode=None):
+def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, attn_p, dpath, coord=None, cproj=None, cmode=None,
+                        rpe=None):
     """n = norm(x) -> (y, qkv, att, lse), y = x + DropPath(drop(proj(PatchAttention(qkv(n))))); qn / kn = (weight, bias), or
     both None for attention without q/k normalisation.  coord / cproj / cmode: add_coords_in_attn (model.py:484-495) — 'qkv' adds
     coord cproj^T to `n` IN PLACE before the qkv product (the caller saves that n: it is what the product's weight gradient reads),
-    'qk' adds it to the q and the k columns of the product."""
+    'qk' adds it to the q and the k columns of the product.  rpe = (rpe_table [3 (2 bnd + 1), H], bnd): the patch attention runs
+    with the relative-position term (enable_rpe, model.py:307-326, :518-527) over the level's grid coordinates."""
     N, C = x.shape
     if cmode == "qkv":
         coord_add_fwd(n, C, C, coord, cproj)
@@ -1298,8 +1340,12 @@ def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, 
         coord_add_fwd(qkv, 2 * C, C, coord, cproj)
     att = torch.empty(N, C, dtype=x.dtype, device=x.device)
     lse = torch.empty(lvl.npad, H, dtype=torch.float32, device=x.device)
-    attention_fwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles,
-                  lvl.n_self_tiles, qn, kn, att, lse, H, C // H, attn_p, mix_seed(seed, 1))
+    if rpe is None:
+        attention_fwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles,
+                      lvl.n_self_tiles, qn, kn, att, lse, H, C // H, attn_p, mix_seed(seed, 1))
+    else:
+        attention_rpe_fwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles,
+                          lvl.n_self_tiles, qn, kn, att, lse, H, C // H, lvl.grid, rpe[0], rpe[1], attn_p, mix_seed(seed, 1))
     if dpath > 0.0:
         br, _ = linear_fwd(att, wp, bp, drop_p=drop_p, seed=seed)
         y = drop_path(br, x, dpath, mix_seed(seed, 5))
@@ -1308,9 +1354,11 @@ def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, 
     return y, qkv, att, lse
 
 
-def selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, qn, kn, wp, lvl, H, p, seed, attn_p, dpath, hand, coord=None, cmode=None):
-    """-> (dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, dcproj); `hand`: the hand-over that may hold dy pre-masked (or None).
-    gq, bq, gk, bk are None when qn = kn = None; dcproj is None without the coordinate term (cmode None)."""
+def selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, qn, kn, wp, lvl, H, p, seed, attn_p, dpath, hand, coord=None, cmode=None,
+                        rpe=None):
+    """-> (dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, dcproj, dtable); `hand`: the hand-over that may hold dy pre-masked (or
+    None).  gq, bq, gk, bk are None when qn = kn = None; dcproj is None without the coordinate term (cmode None), dtable without
+    the relative-position term (rpe None)."""
     N, C = n.shape
     dyb = drop_path(dy, None, dpath, mix_seed(seed, 5)) if dpath > 0.0 else dy
     dz = _masked(dyb, p, seed, hand)
@@ -1320,16 +1368,24 @@ def selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, qn, kn, wp, lvl, H, p, seed,
     # borrowed tail-patch copies go to a small side buffer and are added afterwards (no atomics, no memset)
     dqkv = torch.empty(N, 3 * C, dtype=n.dtype, device=n.device)
     extra = torch.empty(max(lvl.n_extra, 1), 2 * C, dtype=n.dtype, device=n.device)
-    gq, bq, gk, bk = attention_bwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner,
-                                   lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, qn, kn, att,
-                                   datt, lse, dqkv, 3 * C, 0, dqkv, 3 * C, C, 2 * C, 0, 0, H, C // H, attn_p, mix_seed(seed, 1),
-                                   lvl.kext, lvl.ext_pos, lvl.n_extra, extra)
+    dtable = None
+    if rpe is None:
+        gq, bq, gk, bk = attention_bwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner,
+                                       lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, qn, kn, att,
+                                       datt, lse, dqkv, 3 * C, 0, dqkv, 3 * C, C, 2 * C, 0, 0, H, C // H, attn_p, mix_seed(seed, 1),
+                                       lvl.kext, lvl.ext_pos, lvl.n_extra, extra)
+    else:
+        (gq, bq, gk, bk), dtable = attention_rpe_bwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner,
+                                                     lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, qn, kn, att,
+                                                     datt, lse, dqkv, 3 * C, 0, dqkv, 3 * C, C, 2 * C, 0, H, C // H, lvl.grid,
+                                                     rpe[0], rpe[1], attn_p, mix_seed(seed, 1), lvl.kext, lvl.ext_pos,
+                                                     lvl.n_extra, extra)
     dwqkv, dbqkv = linear_wgrad(dqkv, n)
     dcproj = coord_add_wgrad(dqkv, 2 * C, C, coord) if cmode == "qk" else None
     dn = linear_dgrad(dqkv, wqkv)
     if cmode == "qkv":
         dcproj = coord_add_wgrad(dn, C, C, coord)
-    return dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, dcproj
+    return dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, dcproj, dtable
 
 
 def ffn_branch_fwd(n, x, w1, b1, w2, b2, drop_p, seed, dpath):
@@ -1518,10 +1574,11 @@ class SelfAttnFn(torch.autograd.Function):
 
     @_fwd
     def forward(ctx, x, g, b, wqkv, bqkv, qnw, qnb, knw, knb, wp, bp, lvl, H, drop_p, seed, attn_p=0.0, hand_in=None, dpath=0.0,
-                mod=None, bank=None, j=0, coord=None, cproj=None, cmode=None):
+                mod=None, bank=None, j=0, coord=None, cproj=None, cmode=None, rpe_table=None, rpe_bnd=0):
         """qnw = qnb = knw = knb = None: a block without q_norm / k_norm (qk_norm False).  coord / cproj / cmode: the level's
         float coordinates [N, 3], coords_proj.weight [C, 3] and 'qk' | 'qkv' (add_coords_in_attn, model.py:484-495); the node then
-        runs per launch, fp32 storage."""
+        runs per launch, fp32 storage.  rpe_table / rpe_bnd: rpe.rpe_table [3 (2 bnd + 1), H] and pos_bnd (enable_rpe,
+        model.py:307-326): the same rule — per launch, fp32 storage and exact-fp32 operands."""
         N, C = x.shape
         d = C // H
         ctx.meta = (lvl, H, d, drop_p, seed, attn_p)
@@ -1532,7 +1589,7 @@ class SelfAttnFn(torch.autograd.Function):
         if hand_in is not None:
             hand_in.arm(drop_p, seed)
         ctx.site = (bank, j)
-        ctx.comp = coord is None and mod is None and qnw is not None and composites_enabled() and C % 4 == 0 and dpath == 0.0
+        ctx.comp = coord is None and rpe_table is None and mod is None and qnw is not None and composites_enabled() and C % 4 == 0 and dpath == 0.0
         ctx.cmode = None
         if coord is not None:
             if cmode not in ("qk", "qkv") or cproj is None:
@@ -1540,6 +1597,13 @@ class SelfAttnFn(torch.autograd.Function):
             if _capi.BF16:
                 raise NotImplementedError("add_coords_in_attn runs with fp32 activation storage only")
             ctx.cmode = cmode
+        ctx.rpe_bnd = None
+        if rpe_table is not None:
+            if _capi.BF16:
+                raise NotImplementedError("enable_rpe runs with fp32 activation storage only")
+            if rpe_table.shape != (3 * (2 * int(rpe_bnd) + 1), H):
+                raise ValueError(f"SelfAttnFn: rpe_table {tuple(rpe_table.shape)} is not [3 (2 bnd + 1), H] for bnd={rpe_bnd}, H={H}")
+            ctx.rpe_bnd = int(rpe_bnd)
         (wqkvk, wpk), pc = _wk(wqkv, wp)
         ctx.wk, ctx.pc = (wqkvk, wpk), pc
         if ctx.comp:
@@ -1555,9 +1619,10 @@ class SelfAttnFn(torch.autograd.Function):
         n, mean, rstd = ln_fwd(x, g, b, mod=mod, lvl=lvl)
         qn, kn = ((qnw, qnb), (knw, knb)) if qnw is not None else (None, None)
         y, qkv, att, lse = selfattn_branch_fwd(n, x, wqkvk, bqkv, qn, kn, wpk, bp, lvl, H, drop_p, seed, attn_p, dpath,
-                                               coord, cproj, ctx.cmode)
+                                               coord, cproj, ctx.cmode,
+                                               None if rpe_table is None else (rpe_table, ctx.rpe_bnd))
         ctx.coord = coord  # (no gradient flows to it: kept as an attribute, like the level's tables)
-        ctx.save_for_backward(x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd, b, mod)
+        ctx.save_for_backward(x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd, b, mod, rpe_table)
         return y
 
     @_joined
@@ -1576,15 +1641,16 @@ class SelfAttnFn(torch.autograd.Function):
                            lvl.owner, lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, lvl.kext, lvl.ext_pos, lvl.n_extra, lvl.npad,
                            N, C, H, float(d ** -0.5), float(p), int(seed), float(attn_p), mix_seed(seed, 1), ctx.pc, wsm, wsm.numel(),
                            wss, wss_bytes, _counters(dev), cs, _LINK, 0, _capi.stream_ptr(), side)
-            return (dx,) + _grad_views(grads, "self", C, H) + (None,) * 13
-        x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd, b, mod = ctx.saved_tensors
+            return (dx,) + _grad_views(grads, "self", C, H) + (None,) * 15
+        x, g, wqkv, qnw, qnb, knw, knb, wp, n, qkv, att, lse, mean, rstd, b, mod, rpe_table = ctx.saved_tensors
         qn, kn = ((qnw, qnb), (knw, knb)) if qnw is not None else (None, None)
-        dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, dcproj = selfattn_branch_bwd(dy, n, qkv, att, lse, ctx.wk[0], qn, kn, ctx.wk[1],
-                                                                                 lvl, H, p, seed, attn_p, ctx.dpath, ctx.hand_in,
-                                                                                 ctx.coord, ctx.cmode)
+        rpe = None if rpe_table is None else (rpe_table, ctx.rpe_bnd)
+        dn, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp, dcproj, dtable = selfattn_branch_bwd(
+            dy, n, qkv, att, lse, ctx.wk[0], qn, kn, ctx.wk[1], lvl, H, p, seed, attn_p, ctx.dpath, ctx.hand_in, ctx.coord, ctx.cmode,
+            rpe)
         dmod = _dmod(mod, ctx.site)
         dx, dg, db = ln_bwd(dn, x, mean, rstd, g, add=dy, b=b, mod=mod, dmod=dmod, lvl=lvl)
-        return (dx, dg, db, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp) + (None,) * 7 + (dmod, None, None, None, dcproj, None)
+        return (dx, dg, db, dwqkv, dbqkv, gq, bq, gk, bk, dwp, dbp) + (None,) * 7 + (dmod, None, None, None, dcproj, None, dtable, None)
 
 
 class CrossAttnFn(torch.autograd.Function):

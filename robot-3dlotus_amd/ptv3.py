@@ -39,12 +39,27 @@ def _bn(c):
     return nn.BatchNorm1d(c, eps=1e-3, momentum=0.01)
 
 
+class _RPE(nn.Module):
+    """model.py:307-315: the table of the relative-position term, [3 (2 pos_bnd + 1), H], trunc_normal_(std=0.02).  pos_bnd comes
+    from the CONFIGURED patch size by the reference's own expression (15 at 128).  The lookup runs inside the attention kernels
+    (csrc/attention_rpe.hip)."""
+
+    def __init__(self, patch_size, num_heads):
+        super().__init__()
+        self.pos_bnd = ops.rpe_bound(patch_size)
+        self.rpe_num = 2 * self.pos_bnd + 1
+        self.rpe_table = nn.Parameter(torch.zeros(3 * self.rpe_num, num_heads))
+        nn.init.trunc_normal_(self.rpe_table, std=0.02)
+
+
 class _Attn(nn.Module):
-    def __init__(self, c, h, qk_norm=True, coords=False):
-        """coords: False, or add_coords_in_attn 'qk' | 'qkv' (model.py:396-398, 484-495)."""
+    def __init__(self, c, h, qk_norm=True, coords=False, rpe_patch=None):
+        """coords: False, or add_coords_in_attn 'qk' | 'qkv' (model.py:396-398, 484-495).  rpe_patch: None, or the configured
+        patch size of enable_rpe (model.py:390)."""
         super().__init__()
         self.qkv = nn.Linear(c, 3 * c)
         self.proj = nn.Linear(c, c)
+        self.rpe = _RPE(rpe_patch, h) if rpe_patch else None  # registered between proj and q_norm, as the reference does
         # qk_norm False: nn.Identity, as the reference registers (model.py:393-394) — same module names, no state entries
         self.q_norm = nn.LayerNorm(c // h, eps=1e-6) if qk_norm else nn.Identity()
         self.k_norm = nn.LayerNorm(c // h, eps=1e-6) if qk_norm else nn.Identity()
@@ -102,7 +117,12 @@ class Block(nn.Module):
         handed = qk and mods is None
         h_attn, h_mlp = (ops.Handoff(), ops.Handoff()) if handed else (None, None)
         gb, ada = site(self.norm1[0])
-        if a.coords_mode is None:
+        if a.rpe is not None:  # enable_rpe: the table is a differentiable input (the node runs per launch)
+            x = ops.SelfAttnFn.apply(x, *gb, a.qkv.weight, a.qkv.bias, *qkn, a.proj.weight, a.proj.bias, lvl, self.num_heads,
+                                     drop_p, seed, attn_p, h_attn, dpath, *(ada or (None, None, 0)),
+                                     lvl.coord if a.coords_mode else None, a.coords_proj.weight if a.coords_mode else None,
+                                     a.coords_mode, a.rpe.rpe_table, a.rpe.pos_bnd)
+        elif a.coords_mode is None:
             x = ops.SelfAttnFn.apply(x, *gb, a.qkv.weight, a.qkv.bias, *qkn, a.proj.weight, a.proj.bias, lvl, self.num_heads,
                                      drop_p, seed, attn_p, h_attn, dpath, *ada)
         else:  # add_coords_in_attn: the level's float coordinates enter the attention's input (the node runs per launch)
@@ -195,6 +215,7 @@ class PointTransformerV3CA(nn.Module):
     block_cls = Block  # the type _blocks / _block_level index
     plain_attention = False  # whether the class runs qk_norm=False (attention without q/k LayerNorm): the AdaNorm backbone only
     coord_attention = False  # whether the class runs add_coords_in_attn 'qk' / 'qkv': the AdaNorm and the Concat backbone
+    dense_attention = False  # whether the class runs enable_flash False (per-level patch size) and enable_rpe: the same two
 
     def __init__(self, in_channels=6, order=("z", "z-trans", "hilbert", "hilbert-trans"), stride=(2, 2, 2, 2),
                  enc_depths=(2, 2, 2, 6, 2), enc_channels=(32, 64, 128, 256, 512), enc_num_head=(2, 4, 8, 16, 32),
@@ -211,8 +232,21 @@ class PointTransformerV3CA(nn.Module):
             raise ValueError(f"add_coords_in_attn={add_coords_in_attn!r}: one of 'none', 'qk', 'qkv' (model.py:484-495)")
         self.add_coords = add_coords_in_attn if add_coords_in_attn in ("qk", "qkv") else False
         pd = self._pdnorm_unsupported(pdnorm_bn, pdnorm_ln, pdnorm_decouple, pdnorm_adaptive, pdnorm_affine, pdnorm_only_decoder)
-        unsupported = dict(**pd, enable_rpe=enable_rpe, cls_mode=cls_mode,
-                           scaled_cosine_attn=scaled_cosine_attn, not_flash=not enable_flash, not_qk_norm=not qk_norm and not self.plain_attention,
+        # the reference's own rules (model.py:365-374, asserts there): RPE and the two upcast switches belong to the non-flash branch
+        if enable_flash and self.dense_attention:
+            if enable_rpe:
+                raise ValueError("enable_rpe=True with enable_flash=True: \"Set enable_rpe to False when enable Flash Attention\" "
+                                 "(model.py:366-368)")
+            for name, v in (("upcast_attention", upcast_attention), ("upcast_softmax", upcast_softmax)):
+                if v:
+                    raise ValueError(f"{name}=True with enable_flash=True: \"Set {name} to False when enable Flash Attention\" "
+                                     f"(model.py:369-374)")
+        # (enable_flash False: upcast_attention / upcast_softmax are .float() on fp32 tensors — no-ops here)
+        self.enable_flash, self.enable_rpe = bool(enable_flash), bool(enable_rpe)
+        # scaled_cosine_attn stays refused: its flash branch multiplies an (H, 1, 1) parameter into an (N, H, d) tensor, which does
+        # not broadcast for general N; its non-flash branch would need a normalisation backward of its own
+        unsupported = dict(**pd, enable_rpe=enable_rpe and not self.dense_attention, cls_mode=cls_mode,
+                           scaled_cosine_attn=scaled_cosine_attn, not_flash=not enable_flash and not self.dense_attention, not_qk_norm=not qk_norm and not self.plain_attention,
                            not_pre_norm=not pre_norm, no_qkv_bias=not qkv_bias, qk_scale=qk_scale is not None,
                            add_coords=bool(self.add_coords) and not self.coord_attention,
                            depth_lt_1=any(d < 1 for d in list(enc_depths) + list(dec_depths)),
@@ -231,8 +265,9 @@ class PointTransformerV3CA(nn.Module):
         self.proj_drop, self.attn_drop = float(proj_drop), float(attn_drop)
         self.enc_channels, self.dec_channels = list(enc_channels), list(dec_channels) + [enc_channels[-1]]
         self.enc_depths, self.dec_depths = [int(d) for d in enc_depths], [int(d) for d in dec_depths]
+        self.rpe_patch = int(enc_patch_size[0]) if self.enable_rpe else None  # what _add_depth hands to the Blocks' attention
         self.frontend = FrontEnd(self.num_stages, patch_size=enc_patch_size[0], orders=self.order,
-                                 n_patch_orders=max(self.enc_depths + self.dec_depths),
+                                 n_patch_orders=max(self.enc_depths + self.dec_depths), min_count_patches=not self.enable_flash,
                                  conv_widths=[max(e, d) for e, d in zip(self.enc_channels, self.dec_channels)])
         # stochastic-depth schedule, model_ca.py:250-252,316-325: linear in the block index over the whole encoder /
         # decoder; the decoder's per-stage slice is reversed
