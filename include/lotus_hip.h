@@ -371,6 +371,9 @@ int lotus_attention_bwd(const lotus_act_t* q, long q_ld, int q_off, const lotus_
  *             6 attn_rpe_fwd_kernel, 7 attn_rpe_bwd_kernel (lotus_attention_rpe_fwd / _bwd: the exact-fp32 tile kernels with the
  *               relative-position term; precision 0, targ 0, 256 threads, lds_bytes 57 216 forward and 74 112 + 1 536 (2 bnd + 1)
  *               backward; tail bit 2 = attn_rpe_merge_kernel, always set by family 7)
+ *             8 attn_long_fwd_kernel, 9 attn_long_dq_kernel + attn_long_dkv_kernel (lotus_attention_long_fwd / _bwd: tiles of up to
+ *               LOTUS_ATTN_LONG_MAX rows walked in 128-row key images; precision 0, targ 0, 256 threads, lds_bytes 57 344 forward
+ *               and 75 264 backward; tail bits 0 / 1 as below, with kernels of that file)
  *   direction 0 forward, 1 backward
  *   targ      the kernel's template argument: head width D = 32 | 24 | 16 (4), NW = 4 (5), 0 for the tile families
  *   precision the operand mode of the kernel that runs: 0 exact fp32, 1 bf16, 3 bf16x3 (families 3, 4, 5: always 0)
@@ -813,6 +816,53 @@ int lotus_attention_rpe_bwd(const float* q, long q_ld, int q_off, const float* k
                             float* dkn_w, float* dkn_b, int accumulate, int H, int d, float scale, float eps, float drop_p,
                             unsigned long long drop_seed, const int* grid, const float* table, int bnd, float* dtable,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- patch attention above 128 rows per patch (fp32 only, no bf16 twin; csrc/attention_long.hip) ---------------------------------
+ * PointTransformerV3/model.py:529-551: SerializedAttention over patches of enc_patch_size / dec_patch_size = 256, 512, 1024.  A tile
+ * may have q_len, k_len up to LOTUS_ATTN_LONG_MAX; the keys are walked in 128-row images with an online softmax (running maximum
+ * and sum; the accumulator is rescaled between images), all in exact fp32.  Route families 8 (forward) and 9 (backward) of
+ * lotus_attention_last_route: precision 0, targ 0, 256 threads, lds_bytes 57 344 forward and 75 264 backward.
+ *   len_max  the longest q_len / k_len of any tile, DECLARED by the caller (the tile table is device memory): it sizes the grid,
+ *            ceil(len_max / 128) slabs per tile, and is what the entry points can refuse.  Rows of a tile beyond it are not
+ *            computed; they are never read or written out of bounds.
+ *   lotus_attention_long_fwd:  the arguments of lotus_attention_fwd without precision and k_max, then len_max.  PointTransformerV3/
+ *       model.py:529-551.  One block per (128-row query slab of a tile, head).  out, lse (one per (row, head): m + log l), the
+ *       q/k-norm pointers (all four given or all four null, eps as given: the model passes 1e-6; applied while a row image is
+ *       loaded) and the dropout on the probabilities (the mask function of lotus_attention_fwd) as there.  Element number of
+ *       (tile, head h, query i, key j), i and j counted from the tile's q_start / k_start:
+ *           idx = ((tile * H + h) * LOTUS_ATTN_LONG_MAX + i) * LOTUS_ATTN_LONG_MAX + j      (64-bit)
+ *           x = (uint32) idx * 0x9E3779B1 + (uint32) seed;  x ^= (uint32)(idx >> 32) * 0x7FEB352D + (uint32)(seed >> 32);
+ *           x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  keep iff x >= (uint32)(drop_p 2^32) (at least 1), scale 1 / (1 - drop_p)
+ *       (not the numbering of the 128-row kernels: a tile of at most 128 rows gets another mask here than there).
+ *   lotus_attention_long_bwd:  the arguments of lotus_attention_bwd without atomic_out, precision and k_max, then len_max, npos (the
+ *       rows of lse: every q_start + q_len of a tile is <= npos) and the workspace.  PointTransformerV3/model.py:529-551.
+ *       delta = rowsum(dO o O) is computed once (by the dQ kernel, into the workspace).  dQ: one block per (query slab, head) walks
+ *       the key images; dK / dV: one block per (key image, head) walks the query slabs, owns its rows and writes them with plain
+ *       stores, the gradients of borrowed key rows into dkv_extra (kext / ext_pos as at lotus_attention_bwd).  Every tile belongs
+ *       to exactly one block.  The q/k-norm parameter gradients are summed per block in fp32, then over the blocks in ascending
+ *       order in float64.  No atomics: reruns are bit-identical.  workspace: lotus_attention_long_bwd_workspace(nblocks, H,
+ *       len_max, npos) bytes, 8-byte aligned.
+ * LOTUS_E_ARG before any launch, with a message: a null pointer among q, kv, tiles, out (backward: blocks, out, dout, lse, dq,
+ * dkv), H <= 0, d not a multiple of 4 in [4, 32], len_max < 1 or > LOTUS_ATTN_LONG_MAX, drop_p outside [0, 1), some but not all of
+ * the norm pointers, a null norm gradient with the norm, ntiles / nblocks / npos < 0, a short or misaligned workspace, borrowed rows
+ * without dkv_extra / ext_pos / kidx or with k | v column blocks that are not adjacent.  A refused call leaves the route record as
+ * it was, as does ntiles == 0 / nblocks == 0. */
+#define LOTUS_ATTN_LONG_MAX 1024
+int lotus_attention_long_fwd(const float* q, long q_ld, int q_off, const float* kv, long kv_ld, int k_off, int v_off,
+                             const int* qidx, const int* kidx, const int* owner, const int* tiles, int ntiles,
+                             const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b, float* out,
+                             long out_ld, float* lse, int H, int d, float scale, float eps, float drop_p,
+                             unsigned long long drop_seed, int len_max, void* stream);
+size_t lotus_attention_long_bwd_workspace(int nblocks, int H, int len_max, long npos);
+int lotus_attention_long_bwd(const float* q, long q_ld, int q_off, const float* kv, long kv_ld, int k_off, int v_off,
+                             const int* qidx, const int* kidx, const int* owner, const int* tiles, const int* blocks,
+                             int nblocks, const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b,
+                             const float* out, const float* dout, long out_ld, const float* lse, float* dq, long dq_ld,
+                             int dq_off, float* dkv, long dkv_ld, int dk_off, int dv_off, long dkv_part_stride,
+                             const int* kext, const int* ext_pos, int n_extra, float* dkv_extra, float* dqn_w, float* dqn_b,
+                             float* dkn_w, float* dkn_b, int accumulate, int H, int d, float scale, float eps, float drop_p,
+                             unsigned long long drop_seed, int len_max, long npos, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,7 @@ class PointTransformerV3AdaNorm(PointTransformerV3CA):
     plain_attention = True
     coord_attention = True
     dense_attention = True
+    long_patches = True
 
     def __init__(self, *args, pdnorm_bn=True, pdnorm_ln=True, pdnorm_decouple=False, pdnorm_adaptive=True, **kw):
         super().__init__(*args, pdnorm_bn=pdnorm_bn, pdnorm_ln=pdnorm_ln, pdnorm_decouple=pdnorm_decouple,

@@ -108,6 +108,7 @@ class PointTransformerV3Plain(PointTransformerV3CA):
     plain_attention = True
     coord_attention = True
     dense_attention = True
+    long_patches = True
 
     def __init__(self, in_channels=6, *args, **kw):
         super().__init__(in_channels, *args, **kw)

@@ -229,6 +229,20 @@ CONCAT_OVERRIDES["concat_tiny_rpe"] = CONCAT_OVERRIDES["concat_tiny"] + RPE_ATTN
 MP_ADA_OVERRIDES["mp_ada_tiny_rpe"] = MP_ADA_OVERRIDES["mp_ada_tiny"] + RPE_ATTN
 
 
+# patch sizes above 128 (PointTransformerV3/model.py:529-551; the reference's constructors default to 1024) on the AdaNorm and the
+# Concat backbone: the tiny networks at 256 — with (adanorm_tiny, concat_tiny) and without (adanorm_tiny_plain, mp_ada_tiny) q/k
+# LayerNorm — and the shipped YAML with both patch-size lists at 1024.
+def _patches(k, n_enc, n_dec):
+    return ["ptv3_config.enc_patch_size", str([k] * n_enc), "ptv3_config.dec_patch_size", str([k] * n_dec)]
+
+
+ADANORM_OVERRIDES.update({"adanorm_tiny_p256": ADANORM_OVERRIDES["adanorm_tiny"] + _patches(256, 2, 1),
+                          "adanorm_tiny_plain_p256": ADANORM_OVERRIDES["adanorm_tiny_plain"] + _patches(256, 2, 1),
+                          "adanorm_yaml_p1024": _patches(1024, 5, 4)})
+CONCAT_OVERRIDES["concat_tiny_p256"] = CONCAT_OVERRIDES["concat_tiny"] + _patches(256, 2, 1)
+MP_ADA_OVERRIDES["mp_ada_tiny_p256"] = MP_ADA_OVERRIDES["mp_ada_tiny"] + _patches(256, 2, 1)
+
+
 def preset(name="v1"):
     """'v1' / 'tiny': 3D-LOTUS policy; 'peract': the RLBench-18task (PerAct) variant of BASELINE configs[4] (same network;
     its bf16 compute mode is ops.set_gemm_precision("bf16")); 'mp' / 'mp_tiny': 3D-LOTUS++ motion planner (configs[3]);
@@ -241,7 +255,9 @@ def preset(name="v1"):
     'adanorm_tiny_qk' / 'adanorm_tiny_qkv' / 'adanorm_yaml_qk' / 'concat_tiny_qk' / 'concat_tiny_qkv' / 'mp_ada_tiny_qkv': their
     base preset with add_coords_in_attn 'qk' / 'qkv' (adanorm_tiny_qk on adanorm_tiny_plain: qk_norm False);
     'adanorm_tiny_dense': adanorm_tiny with enable_flash False; 'adanorm_tiny_rpe' / 'adanorm_tiny_plain_rpe' / 'concat_tiny_rpe' /
-    'mp_ada_tiny_rpe' / 'adanorm_yaml_rpe': their base preset with enable_flash False and enable_rpe True."""
+    'mp_ada_tiny_rpe' / 'adanorm_yaml_rpe': their base preset with enable_flash False and enable_rpe True;
+    'adanorm_tiny_p256' / 'adanorm_tiny_plain_p256' / 'concat_tiny_p256' / 'mp_ada_tiny_p256': their base preset with every patch
+    size 256; 'adanorm_yaml_p1024': the shipped YAML with every patch size 1024."""
     if name in ("mp", "mp_tiny", "mp_tinyctx"):
         model = copy.deepcopy(_YAML_MODEL)
         model["model_class"] = _YAML_MP_DELTA["model_class"]

@@ -12,6 +12,8 @@
 #define LOTUS_ATTN_XQ2 5    // xq2_fwd_kernel<4> / xq2_bwd_kernel<4>
 #define LOTUS_ATTN_RPE_FWD 6  // attn_rpe_fwd_kernel<NORM> (attention_rpe.hip: lotus_attention_rpe_fwd)
 #define LOTUS_ATTN_RPE_BWD 7  // attn_rpe_bwd_kernel<NORM> (attention_rpe.hip: lotus_attention_rpe_bwd)
+#define LOTUS_ATTN_LONG_FWD 8  // attn_long_fwd_kernel<NORM> (attention_long.hip: lotus_attention_long_fwd)
+#define LOTUS_ATTN_LONG_BWD 9  // attn_long_dq_kernel<NORM> + attn_long_dkv_kernel<NORM> (attention_long.hip: lotus_attention_long_bwd)
 
 #define LOTUS_ATTN_TAIL_FIXUP 1      // attn_extra_fixup_kernel follows the main kernel
 #define LOTUS_ATTN_TAIL_LN_REDUCE 2  // attn_ln_reduce_kernel follows

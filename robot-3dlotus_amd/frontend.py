@@ -24,6 +24,8 @@ ORDERS = ("z", "z-trans", "hilbert", "hilbert-trans")
 # longest context (instruction tokens of one cloud) the cross attention is built for: the tile kernels of csrc/attention.hip
 # keep one 128-row key image in LDS and index it by tid < 128 (the reference hands over at most 77 CLIP tokens + 1)
 MAX_CTX = 128
+# patch sizes above 128: the tiles of csrc/attention_long.hip (key images of 128 rows, at most LOTUS_ATTN_LONG_MAX = 1024 per tile)
+LONG_PATCH_SIZES = (256, 512, 1024)
 
 
 class _Arena:
@@ -55,7 +57,7 @@ class Level:
     __slots__ = ("n", "counts", "off", "off_host", "grid", "batch", "code", "order", "inverse", "depth", "nbr27",
                  "nbr125", "gidx", "owner", "kext", "ext_pos", "n_extra", "npad", "self_tiles", "self_blocks", "n_self_tiles", "ca_tiles",
                  "ca_blocks", "n_ca_tiles", "n_ca_blocks", "ca_groups", "cluster", "seg_start", "members",
-                 "coord", "parent", "n_dup", "patch", "_views", "ca_kmax", "_patch_args", "tap_plan", "K")
+                 "coord", "parent", "n_dup", "patch", "_views", "ca_kmax", "_patch_args", "tap_plan", "K", "tile_max")
 
     def for_order(self, k):
         """The level as the k-th block of a stage sees it: `Block(order_index = i % len(order))` attends along curve slot k
@@ -95,7 +97,13 @@ class FrontEnd:
                  min_count_patches=False):
         """min_count_patches: the patching of the reference's non-flash attention (enable_flash False, model.py:469-472) — level s
         is patched at K_s = min(patch_size, fewest points any cloud has at level s) instead of patch_size, so every patch has
-        exactly K_s rows.  The counts are on the host when the plans are made: no extra copy, no extra kernel."""
+        exactly K_s rows.  The counts are on the host when the plans are made: no extra copy, no extra kernel.
+        patch_size: any value up to 128, or one of LONG_PATCH_SIZES (a tile then has up to patch_size rows and the attention runs
+        on the kernels of csrc/attention_long.hip wherever a level's longest tile, Level.tile_max, is above 128 rows); anything else
+        raises ValueError."""
+        if patch_size > 128 and patch_size not in LONG_PATCH_SIZES:
+            raise ValueError(f"patch_size={patch_size}: above 128 the patch attention is built for {LONG_PATCH_SIZES} "
+                             f"(csrc/attention_long.hip)")
         self.n_levels = n_levels
         self.min_count_patches = bool(min_count_patches)
         # widest 3^3 convolution of every level (None: unknown): levels with few rows and wide layers get a tap plan
@@ -303,7 +311,7 @@ class FrontEnd:
             plans.append(dict(off=push(off), offp=push(offp), tiles=push(tiles), blocks=push(blocks),
                               ca_tiles=push(ca_tiles), ca_blocks=push(ca_blocks), n_tiles=nt_self,
                               n_ca_tiles=n_ca, n_ca_blocks=B * G, G=G, npad=int(offp[-1]),
-                              off_host=off, K=K))
+                              off_host=off, K=K, tile_max=int(tiles[:, 1].max()) if nt_self else 0))
         ntab = sum(a.size for a in host_tabs)
         tabs_h = torch.empty(ntab, dtype=torch.int32, pin_memory=True)  # pinned: the upload must not drain the queue
         np.concatenate(host_tabs, out=tabs_h.numpy())
@@ -378,6 +386,7 @@ class FrontEnd:
                 lv.nbr125 = empty(125, n)
                 call("lotus_fe_neighbours", lv.grid, lv.batch, n, 5, lv.nbr125, ws_n, ws_n.numel())
             lv.npad, lv.K = pl["npad"], pl["K"]
+            lv.tile_max = pl["tile_max"]  # rows of the longest self-attention tile: above 128 the long kernels run (ops.long_tiles)
             K = lv.K
             lv.gidx = empty(lv.npad)
             lv.owner = empty(lv.npad)

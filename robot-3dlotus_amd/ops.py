@@ -62,12 +62,15 @@ def last_conv_route():
 AttnRoute = collections.namedtuple("AttnRoute", "family direction targ precision norm threads lds_bytes tail")
 ATTN_FWD, ATTN_BWD, ATTN_BWD2, ATTN_XQ, ATTN_XQ2 = range(1, 6)
 ATTN_RPE_FWD, ATTN_RPE_BWD = 6, 7  # lotus_attention_rpe_fwd / _bwd (csrc/attn_route.h)
+ATTN_LONG_FWD, ATTN_LONG_BWD = 8, 9  # lotus_attention_long_fwd / _bwd: tiles above 128 rows (csrc/attn_route.h)
+ATTN_LONG_MAX = 1024  # LOTUS_ATTN_LONG_MAX (include/lotus_hip.h): the longest tile the long kernels take
 
 
 def last_attn_route():
     """The kernel this thread's last attention launch was given to (lotus_attention_last_route; fields in include/lotus_hip.h):
     family 1 tile forward, 2 tile backward on bf16 / bf16x3 operands, 3 tile backward in fp32, 4 / 5 one lane per query (keys in
-    LDS / in registers), 6 / 7 tile forward / backward with the relative-position term; direction 0 fwd / 1 bwd; template argument; operand precision; with the q/k norm; threads; dynamic LDS
+    LDS / in registers), 6 / 7 tile forward / backward with the relative-position term, 8 / 9 forward / backward over tiles above
+    128 rows (key images walked with an online softmax); direction 0 fwd / 1 bwd; template argument; operand precision; with the q/k norm; threads; dynamic LDS
     bytes; tail (bit 0 fix-up, bit 1 norm-gradient reduction, bit 2 table-gradient merge follow).  Set when the kernel is chosen, so it is there after a
     launch that failed, too."""
     out = (ctypes.c_int * 8)()
@@ -1157,6 +1160,45 @@ def attention_rpe_bwd(q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner
     return grads, dtable
 
 
+def attention_long_fwd(q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, ntiles, qn, kn, out, lse, H, d, len_max,
+                       drop_p=0.0, seed=0):
+    """attention_fwd over tiles of up to ATTN_LONG_MAX rows (patch sizes 256, 512, 1024; model.py:529-551): len_max = the longest
+    q_len / k_len of a tile, declared by the caller.  Exact fp32, fp32 storage; its own dropout numbering (include/lotus_hip.h)."""
+    assert not _capi.BF16, "the patch attention above 128 rows runs with fp32 activation storage"
+    qn, kn = _qk_norms(qn, kn)
+    call("lotus_attention_long_fwd", q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, ntiles,
+         qn[0], qn[1], kn[0], kn[1], out, out.stride(0), lse, H, d, float(d ** -0.5), 1e-6, float(drop_p), int(seed), int(len_max))
+
+
+def long_tiles(lvl):
+    """Whether the level's patch attention runs on the long kernels: its longest self-attention tile has more than 128 rows
+    (Level.tile_max, from the host plan).  A level of a model with patch size 256 / 512 / 1024 whose clouds all fit 128-row tiles
+    keeps the 128-row kernels and its composite."""
+    return getattr(lvl, "tile_max", 0) > 128
+
+
+_LONG_WS_SLOT = 9  # workspace slot of the long-patch backward: delta and the norm partials (main stream)
+
+
+def attention_long_bwd(q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, blocks, nblocks, qn, kn, out,
+                       dout, lse, dq, dq_ld, dq_off, dkv, dkv_ld, dk_off, dv_off, part_stride, H, d, len_max, drop_p=0.0,
+                       seed=0, kext=None, ext_pos=None, n_extra=0, dkv_extra=None):
+    """-> the gradients of q_norm / k_norm (weight, bias, weight, bias); four None when qn = kn = None.  Plain stores, no atomics;
+    lse is [npos, H] and every tile lies inside its rows."""
+    assert not _capi.BF16, "the patch attention above 128 rows runs with fp32 activation storage"
+    dev = q.device
+    plain = qn is None and kn is None
+    qn, kn = _qk_norms(qn, kn)
+    grads = [None] * 4 if plain else [torch.empty(d, dtype=torch.float32, device=dev) for _ in range(4)]
+    npos = int(lse.shape[0])
+    ws = WS.get(query("lotus_attention_long_bwd_workspace", nblocks, H, int(len_max), npos), dev, slot=_LONG_WS_SLOT)
+    call("lotus_attention_long_bwd", q, q_ld, q_off, kv, kv_ld, k_off, v_off, qidx, kidx, owner, tiles, blocks, nblocks,
+         qn[0], qn[1], kn[0], kn[1], out, dout, out.stride(0), lse, dq, dq_ld, dq_off, dkv, dkv_ld, dk_off, dv_off,
+         part_stride, kext, ext_pos, n_extra, dkv_extra, grads[0], grads[1], grads[2], grads[3], 0, H, d, float(d ** -0.5), 1e-6,
+         float(drop_p), int(seed), int(len_max), npos, ws, ws.numel())
+    return grads
+
+
 # ------------------------------------------------------------------------------------ composite fast path
 # One C call per sub-block direction (csrc/blocks.cpp) instead of one per launch: same entry points, same order, same
 # streams -> bit-identical results (tests/test_gpu_blocks.py), ~70 % less interpreter time inside the sub-blocks.  The
@@ -1340,7 +1382,12 @@ def selfattn_branch_fwd(n, x, wqkv, bqkv, qn, kn, wp, bp, lvl, H, drop_p, seed, 
         coord_add_fwd(qkv, 2 * C, C, coord, cproj)
     att = torch.empty(N, C, dtype=x.dtype, device=x.device)
     lse = torch.empty(lvl.npad, H, dtype=torch.float32, device=x.device)
-    if rpe is None:
+    if long_tiles(lvl):  # tiles above 128 rows: key images walked with an online softmax (csrc/attention_long.hip)
+        if rpe is not None:
+            raise NotImplementedError("the relative-position term is built for patches of at most 128 rows")
+        attention_long_fwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles,
+                           lvl.n_self_tiles, qn, kn, att, lse, H, C // H, lvl.tile_max, attn_p, mix_seed(seed, 1))
+    elif rpe is None:
         attention_fwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner, lvl.self_tiles,
                       lvl.n_self_tiles, qn, kn, att, lse, H, C // H, attn_p, mix_seed(seed, 1))
     else:
@@ -1369,7 +1416,12 @@ def selfattn_branch_bwd(dy, n, qkv, att, lse, wqkv, qn, kn, wp, lvl, H, p, seed,
     dqkv = torch.empty(N, 3 * C, dtype=n.dtype, device=n.device)
     extra = torch.empty(max(lvl.n_extra, 1), 2 * C, dtype=n.dtype, device=n.device)
     dtable = None
-    if rpe is None:
+    if long_tiles(lvl):
+        gq, bq, gk, bk = attention_long_bwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner,
+                                            lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, qn, kn, att,
+                                            datt, lse, dqkv, 3 * C, 0, dqkv, 3 * C, C, 2 * C, 0, H, C // H, lvl.tile_max, attn_p,
+                                            mix_seed(seed, 1), lvl.kext, lvl.ext_pos, lvl.n_extra, extra)
+    elif rpe is None:
         gq, bq, gk, bk = attention_bwd(qkv, 3 * C, 0, qkv, 3 * C, C, 2 * C, lvl.gidx, lvl.gidx, lvl.owner,
                                        lvl.self_tiles, lvl.self_blocks, lvl.n_self_tiles, qn, kn, att,
                                        datt, lse, dqkv, 3 * C, 0, dqkv, 3 * C, C, 2 * C, 0, 0, H, C // H, attn_p, mix_seed(seed, 1),
@@ -1589,7 +1641,10 @@ class SelfAttnFn(torch.autograd.Function):
         if hand_in is not None:
             hand_in.arm(drop_p, seed)
         ctx.site = (bank, j)
-        ctx.comp = coord is None and rpe_table is None and mod is None and qnw is not None and composites_enabled() and C % 4 == 0 and dpath == 0.0
+        ctx.comp = (coord is None and rpe_table is None and mod is None and qnw is not None and composites_enabled() and C % 4 == 0
+                    and dpath == 0.0 and not long_tiles(lvl))  # (tiles above 128 rows: per launch, as the coordinate and RPE terms)
+        if long_tiles(lvl) and _capi.BF16:
+            raise NotImplementedError("patch sizes above 128 run with fp32 activation storage only")
         ctx.cmode = None
         if coord is not None:
             if cmode not in ("qk", "qkv") or cproj is None:

@@ -421,6 +421,11 @@ class SimplePolicyPTV3AdaNorm(SimplePolicyPTV3CA):
             if mode != "fp32":  # the patch attention with the relative-position term exists as exact-fp32 kernels only
                 raise NotImplementedError(f"SimplePolicyPTV3AdaNorm with enable_rpe=True is built for gemm_precision None / 'fp32' "
                                           f"only, got {mode!r}")
+        if self.ptv3_model.patch_size > 128:
+            mode = self.gemm_precision or ops.get_gemm_precision()
+            if mode != "fp32":  # the patch attention above 128 rows per patch exists as exact-fp32 kernels only
+                raise NotImplementedError(f"SimplePolicyPTV3AdaNorm with patch sizes above 128 is built for gemm_precision None / 'fp32' "
+                                          f"only, got {mode!r}")
         return super().forward(batch, compute_loss, **kwargs)
 
 

@@ -216,6 +216,7 @@ class PointTransformerV3CA(nn.Module):
     plain_attention = False  # whether the class runs qk_norm=False (attention without q/k LayerNorm): the AdaNorm backbone only
     coord_attention = False  # whether the class runs add_coords_in_attn 'qk' / 'qkv': the AdaNorm and the Concat backbone
     dense_attention = False  # whether the class runs enable_flash False (per-level patch size) and enable_rpe: the same two
+    long_patches = False  # whether the class runs patch sizes 256 / 512 / 1024 (csrc/attention_long.hip): the same two
 
     def __init__(self, in_channels=6, order=("z", "z-trans", "hilbert", "hilbert-trans"), stride=(2, 2, 2, 2),
                  enc_depths=(2, 2, 2, 6, 2), enc_channels=(32, 64, 128, 256, 512), enc_num_head=(2, 4, 8, 16, 32),
@@ -251,7 +252,10 @@ class PointTransformerV3CA(nn.Module):
                            add_coords=bool(self.add_coords) and not self.coord_attention,
                            depth_lt_1=any(d < 1 for d in list(enc_depths) + list(dec_depths)),
                            stride_ne_2=any(s != 2 for s in stride),
-                           patch_ne_128=any(p > 128 for p in list(enc_patch_size) + list(dec_patch_size)))
+                           patch_ne_128=any(p > 128 for p in list(enc_patch_size) + list(dec_patch_size)) and not self.long_patches,
+                           # the table lookups of the relative-position term are in the 128-row kernels only
+                           rpe_long_patch=bool(enable_rpe) and self.long_patches and
+                           any(p > 128 for p in list(enc_patch_size) + list(dec_patch_size)))
         bad = [k for k, v in unsupported.items() if v]
         if bad:
             raise NotImplementedError(f"lotus-hip builds the published 3D-LOTUS configuration family only; unsupported: {bad}")
@@ -265,6 +269,7 @@ class PointTransformerV3CA(nn.Module):
         self.proj_drop, self.attn_drop = float(proj_drop), float(attn_drop)
         self.enc_channels, self.dec_channels = list(enc_channels), list(dec_channels) + [enc_channels[-1]]
         self.enc_depths, self.dec_depths = [int(d) for d in enc_depths], [int(d) for d in dec_depths]
+        self.patch_size = int(enc_patch_size[0])
         self.rpe_patch = int(enc_patch_size[0]) if self.enable_rpe else None  # what _add_depth hands to the Blocks' attention
         self.frontend = FrontEnd(self.num_stages, patch_size=enc_patch_size[0], orders=self.order,
                                  n_patch_orders=max(self.enc_depths + self.dec_depths), min_count_patches=not self.enable_flash,
