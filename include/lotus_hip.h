@@ -210,7 +210,8 @@ int lotus_subm_conv(int mode, const lotus_act_t* x, const float* w, const float*
  * row nbr[T/2][p]): the true input gradient of mode 0 is dx[q] = [rep[q] == q] * sum_t W_t^T sum_{p in voxel(q) - d_t} dy[p].
  * lotus_conv_dup_fold writes dyr[r] = sum of dy over the points of r's voxel for representatives r (0 elsewhere), walking
  * the points in sorted (code, index) order `order0` (code0 = curve code per point; fixed order -> deterministic); mode 1
- * on dyr then yields the gradient for representatives, and lotus_conv_dup_mask resets the other rows to `add` (or 0). */
+ * on dyr then yields the gradient for representatives, and lotus_conv_dup_mask resets the other rows to `add` (or 0).  The fold takes widths that are
+ * multiples of 4 (it runs on the output side); the mask takes any width: the stem's input gradient has 7 columns. */
 int lotus_conv_dup_fold(const lotus_act_t* dy, const long long* code0, const int* order0, int n, int C, lotus_act_t* dyr,
                         void* stream);
 int lotus_conv_dup_mask(lotus_act_t* dx, const lotus_act_t* add, const int* rep, int n, int C, void* stream);

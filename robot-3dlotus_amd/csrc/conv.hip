@@ -946,6 +946,14 @@ static __global__ void conv_dup_mask_kernel(act_t* __restrict__ dx, const act_t*
   if (i >= n || rep[i] == i) return;
   st4q(dx, id, add ? ld4q(add, id) : make_float4(0.f, 0.f, 0.f, 0.f));
 }
+// ... and one thread per (row, column) for widths that are no multiple of 4: the stem's input gradient at 7 columns
+static __global__ void conv_dup_mask1_kernel(act_t* __restrict__ dx, const act_t* __restrict__ add, const int* __restrict__ rep,
+                                      int n, int C) {
+  const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = (int)(id / C);
+  if (i >= n || rep[i] == i) return;
+  st1(dx + id, add ? ld1(add + id) : 0.f);
+}
 
 int lotus_conv_dup_fold(const act_t* dy, const long long* code0, const int* order0, int n, int C, act_t* dyr,
                         void* stream) {
@@ -958,10 +966,15 @@ int lotus_conv_dup_fold(const act_t* dy, const long long* code0, const int* orde
   return LOTUS_OK;
 }
 int lotus_conv_dup_mask(act_t* dx, const act_t* add, const int* rep, int n, int C, void* stream) {
-  LOTUS_CHECK_ARG(dx && rep && n >= 0 && C > 0 && C % 4 == 0, "lotus_conv_dup_mask: bad arguments");
+  LOTUS_CHECK_ARG(dx && rep && n >= 0 && C > 0, "lotus_conv_dup_mask: bad arguments");
   if (n == 0) return LOTUS_OK;
-  const long total = (long)n * (C / 4);
-  LOTUS_LAUNCH(conv_dup_mask_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, add, rep, n, C / 4);
+  if (C % 4 == 0) {
+    const long total = (long)n * (C / 4);
+    LOTUS_LAUNCH(conv_dup_mask_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, add, rep, n, C / 4);
+  } else {
+    const long total = (long)n * C;
+    LOTUS_LAUNCH(conv_dup_mask1_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, add, rep, n, C);
+  }
   LOTUS_LAUNCH_CHECK("lotus_conv_dup_mask");
   return LOTUS_OK;
 }
