@@ -54,11 +54,8 @@ def ctx_taps_bwd(dy, lvl, T):
 
 def split_stem_weight(w, c_pc):
     """stem.conv.weight [cout, 5, 5, 5, c_pc + Cc] -> (W_pc [cout, 5, 5, 5, c_pc], W_ctx [T * cout, Cc] tap-major), contiguous
-    differentiable slices: autograd carries both gradients back into the one parameter."""
-    cout, T = w.shape[0], w.shape[1] * w.shape[2] * w.shape[3]
-    w_pc = w[..., :c_pc].contiguous()
-    w_ctx = w[..., c_pc:].reshape(cout, T, -1).permute(1, 0, 2).reshape(T * cout, -1)
-    return w_pc, w_ctx.contiguous()
+    differentiable: ops.SplitStemWeightFn carries both gradients back into the one parameter, assembled in one gradient slab."""
+    return ops.SplitStemWeightFn.apply(w, c_pc)
 
 
 def ctx_stem_pre(pc, cvec, w_pc, w_ctx, lvl):

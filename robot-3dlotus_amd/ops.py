@@ -2046,6 +2046,40 @@ class StemFn(torch.autograd.Function):
         return dx, dcw, dg, db, None, None, None, None, dmod, None, None
 
 
+class SplitStemWeightFn(torch.autograd.Function):
+    """stem.conv.weight [cout, 5, 5, 5, c_pc + Cc] -> (W_pc [cout, 5, 5, 5, c_pc], W_ctx [T * cout, Cc] tap-major), the two
+    operands of concat.CtxStemFn.  One node instead of autograd's slices, so that the gradient of the ONE parameter — three
+    quarters of the gradient floats of the tiny Concat policy — is assembled in a slab of _grad_slab like every other weight
+    gradient (a data-parallel reducer then owns that memory) by two strided copies: no zero-filled full-size temporaries, no sum."""
+
+    @staticmethod
+    def forward(ctx, w, c_pc):
+        ctx.meta = (tuple(w.shape), int(c_pc))
+        cout, T = w.shape[0], w.shape[1] * w.shape[2] * w.shape[3]
+        w_pc = w[..., :c_pc].contiguous()
+        w_ctx = w[..., c_pc:].reshape(cout, T, -1).permute(1, 0, 2).reshape(T * cout, -1)
+        return w_pc, w_ctx.contiguous()
+
+    @staticmethod
+    def backward(ctx, dw_pc, dw_ctx):
+        shape, c_pc = ctx.meta
+        cout, T = shape[0], shape[1] * shape[2] * shape[3]
+        src = dw_pc if dw_pc is not None else dw_ctx
+        if _JOIN == "end":
+            sync_side_stream()  # (the copies below are ATen kernels of the current stream; the operands come from the side stream)
+        n = cout * T * shape[4]
+        dw = _grad_slab(n, src.device)[:n].view(shape)
+        if dw_pc is None:
+            dw[..., :c_pc].zero_()
+        else:
+            dw[..., :c_pc].copy_(dw_pc)
+        if dw_ctx is None:
+            dw[..., c_pc:].zero_()
+        else:
+            dw[..., c_pc:].copy_(dw_ctx.reshape(T, cout, -1).permute(1, 0, 2).reshape(cout, *shape[1:4], -1))
+        return dw, None
+
+
 class PoolFn(torch.autograd.Function):
     """SerializedPooling: GELU(BN(segment_max(Linear(x))))   (model.py:760-790)."""
 

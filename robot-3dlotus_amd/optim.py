@@ -176,13 +176,23 @@ class AdamW(torch.optim.Optimizer):
 
     # ---- public ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def clip_grad_norm_(self, max_norm):
+    def clip_grad_norm_(self, max_norm, reducer=None):
         """Global L2 norm of all gradients + clip coefficient, on the device.  Returns the norm (0-dim tensor, no host
-        sync); the gradients themselves are left untouched — the following step() applies the coefficient."""
+        sync); the gradients themselves are left untouched — the following step() applies the coefficient.
+
+        reducer: the parallel.GradReducer of a data-parallel step (after its finish()), as for step(reducer=...): the norm is
+        taken over the slices of its flat, rank-averaged buffer — the gradients that step will apply.  `.grad` is not that set:
+        the reducer resets it to None on usage flags that are one step old, so in the step a parameter turns used the norm
+        over `.grad` leaves out a gradient the update then applies.  A slot no rank wrote is zeros and adds nothing.  Without
+        a reducer (or with one that ran no collectives, whose buffer is not zero-filled) the norm is over `.grad`."""
         if not self._tables_ok():
             self._build_tables()
         tb = self._tables
-        gp = torch.tensor([0 if p.grad is None else p.grad.data_ptr() for p, _ in tb["plist"]], dtype=torch.int64).pin_memory()
+        if reducer is not None and reducer.used_mask is not None:
+            gp = [reducer.view_of(p).data_ptr() for p, _ in tb["plist"]]
+        else:
+            gp = [0 if p.grad is None else p.grad.data_ptr() for p, _ in tb["plist"]]
+        gp = torch.tensor(gp, dtype=torch.int64).pin_memory()
         gp = gp.to(tb["dev"], non_blocking=True)
         out = torch.empty(2, dtype=torch.float32, device=tb["dev"])
         call("lotus_grad_norm", gp, tb["numel"], tb["chunks"], tb["nchunks"], tb["partial"], out, float(max_norm))

@@ -185,7 +185,8 @@ class GradReducer:
     backward.  Parameters that got no gradient in the learning pass form a trailing "cold" bucket.
 
     Protocol per optimisation step:  zero_grad();  [with no_sync(): backward of micro-batches 1..k-1];  backward of the
-    last micro-batch;  finish().  Every bucket is all-reduced exactly once per step on every rank — from its hook when
+    last micro-batch;  finish()  (zero_grad() may as well END the step, behind the optimiser: the constructor has cleared the
+    gradients for the first one).  Every bucket is all-reduced exactly once per step on every rank — from its hook when
     all its gradients arrived, else in finish() with the slots of gradient-less parameters zeroed — so ranks whose
     parameter usage differs stay in lock-step (what DistributedDataParallel(find_unused_parameters=True) achieves with
     its usage bitmap, which finish() mirrors with one MAX all-reduce of a per-parameter flag: a parameter no rank
@@ -204,7 +205,8 @@ class GradReducer:
         self._cap = int(bucket_mb * (1 << 20) / 4)
         self._layout(list(reversed(self.params)), [])
         # gradient slabs of the backward nodes (ops.GRAD_ARENA): recorded in the learning pass, served from the flat buffer after it
-        self._slab_rec, self._slab_seq, self._slab_i, self._pslab, self._arena_off = [], None, 0, {}, dev.type != "cuda"
+        self._slab_rec, self._slab_seq, self._slab_i, self._pslab = [], None, 0, {}
+        self._arena_off = dev.type != "cuda" and not self.arena_on_host
         self._handles = []
         self.exposed_events = []
         self._avg = (self.world > 1 or self._force) and dist.get_backend(group) == "nccl"  # RCCL averages in the collective
@@ -246,32 +248,42 @@ class GradReducer:
         for p in self.params:
             p.grad = None
             self._hook_handles.append(p.register_post_accumulate_grad_hook(self._hook))
+        # the slabs are recorded from here on, not from the first zero_grad(): a trainer whose steps END with zero_grad() runs its
+        # first (learning) backward before any, and would otherwise never engage the arena
+        ops.GRAD_ARENA = None if self._arena_off else self._arena
 
     def _layout(self, order, cold, slabs=None):
         """Contiguous buckets of >= cap elements over `order`, then one bucket with the `cold` parameters; every parameter
         gets a view into the flat buffer.  slabs = (sizes, where): the gradient slabs of the backward nodes learnt in the first
         pass — where[p] = (slab, offset in floats) for a parameter whose gradient is a view of slab number `slab`.  A slab is
-        laid out WHOLE (its node's own layout, 256-byte aligned) at the place of its first-arriving parameter, so that the node
-        can be handed that slice as its output buffer (_arena) and its gradients need no pack copy."""
+        laid out WHOLE (its node's own layout) at the place of its first-arriving parameter, so that the node can be handed that
+        slice as its output buffer (_arena) and its gradients need no pack copy.  Every slab is 256-byte aligned: the flat
+        buffer's base is, a slab's base is rounded up to 64 floats (the zeros in front of it belong to its bucket and are
+        all-reduced with it) and its size is padded to 64 floats.  A pure function of (order, cold, slabs): every rank lays
+        out alike."""
         import numpy as np
         sizes_, where = slabs if slabs else ([], {})
-        # layout units in arrival order: ("slab", id, floats, params) or ("param", p, floats, [p])
-        units, seen_slab = [], {}
+        # layout units in arrival order: ["slab", id, floats, params, padding in front] or ["param", p, floats, [p], 0]
+        units, seen_slab, total = [], {}, 0
         for p in order:
             w = where.get(p)
             if w is None:
-                units.append(["param", p, p.numel(), [p]])
+                u = ["param", p, p.numel(), [p], 0]
             elif w[0] in seen_slab:
                 seen_slab[w[0]][3].append(p)
+                continue
             else:
-                u = ["slab", w[0], (sizes_[w[0]] + 63) // 64 * 64, [p]]
-                seen_slab[w[0]] = u
-                units.append(u)
-        total = sum(u[2] for u in units) + sum(p.numel() for p in cold)
+                u = seen_slab[w[0]] = ["slab", w[0], (sizes_[w[0]] + 63) // 64 * 64, [p], -total % 64]
+            units.append(u)
+            total += u[4] + u[2]
+        total += sum(p.numel() for p in cold)
         if slabs is not None or getattr(self, "flat", None) is None or self.flat.numel() != total:
-            self.flat = torch.zeros(total, dtype=torch.float32, device=self.params[0].device)
+            # (the host allocator aligns to 64 bytes only: over-allocate and start at the first 256-byte boundary)
+            raw = torch.zeros(total + 63, dtype=torch.float32, device=self.params[0].device)
+            skip = (-raw.data_ptr() // 4) % 64
+            self.flat = raw[skip:skip + total]
         self.buckets, self._bparams, self._bviews, self._slot = [], [], [], {}
-        self._slab_at = {}
+        self._slab_at, self._slab_bucket = {}, {}
         state = dict(p=[], v=[], n=0, offset=0, start=0)
 
         def close():
@@ -285,7 +297,7 @@ class GradReducer:
         # backward ends), so the order's tail is cut into buckets of <= cap/32, cap/8 and cap/2 elements (1 / 4 / 16 MB at
         # the default 32 MB) counted from the end; everything before them follows the >= cap rule.  (20 MB of exposed
         # all-reduce at the end of every step otherwise: the encoder's level-2 gradients arrive ~3 ms before the stem's.)
-        cuts, end, usz = set(), len(units), [u[2] for u in units]
+        cuts, end, usz = set(), len(units), [u[2] + u[4] for u in units]
         if sum(usz) >= 2 * self._cap and os.environ.get("LOTUS_DIAG_NO_TAPER") != "1":
             for tail_cap in (self._cap // 32, self._cap // 8, self._cap // 2):
                 n, i = 0, end
@@ -297,19 +309,19 @@ class GradReducer:
                 cuts.add(i)  # a bucket boundary in front of units[i]
                 end = i
         first_tail = min(cuts) if cuts else len(units)
-        for k, (kind, ident, n, ps) in enumerate(units):
+        for k, (kind, ident, n, ps, pad) in enumerate(units):
             if k in cuts:
                 close()
-            base = state["offset"]
+            base = state["offset"] + pad
             if kind == "slab":
-                self._slab_at[ident] = base
+                self._slab_at[ident], self._slab_bucket[ident] = base, len(self.buckets)
             for p in ps:
                 off = base + (where[p][1] if kind == "slab" else 0)
                 self._slot[p] = len(self.buckets)
                 state["p"].append(p)
                 state["v"].append(self.flat[off:off + p.numel()].view_as(p))
-            state["n"] += n
-            state["offset"] += n
+            state["n"] += pad + n
+            state["offset"] += pad + n
             if k < first_tail and state["n"] >= self._cap:
                 close()
         close()
@@ -323,27 +335,53 @@ class GradReducer:
         self._view = {p: v for ps, vs in zip(self._bparams, self._bviews) for p, v in zip(ps, vs)}
         index = {p: i for i, p in enumerate(self.params)}
         self._bindex = [np.asarray([index[p] for p in ps], dtype=np.int64) for ps in self._bparams]
+        # per bucket: its slabs as (slab, places of the slab's parameters in the bucket's lists) — _flush asks whether a served
+        # slab holds its owners' gradients
+        pos = {p: j for ps in self._bparams for j, p in enumerate(ps)}
+        self._bslabs = [[] for _ in self.buckets]
+        for kind, ident, _, ps, _ in units:
+            if kind == "slab":
+                self._bslabs[self._slab_bucket[ident]].append((ident, [pos[p] for p in ps]))
         self._rearm()
 
     def _arena(self, n, dev):
         """ops.GRAD_ARENA while this reducer's backward runs: the output slab of the next backward node.  Learning pass: a
         plain tensor, remembered so that the hooks can tell which parameter's gradient lives where in it.  Afterwards: the slab's
-        place in the flat buffer, as long as the nodes ask in the learnt order with the learnt sizes (anything else gets a
-        plain tensor for the rest of the step and is packed by copy as before)."""
+        place in the flat buffer, as long as the nodes ask with the learnt sizes at the learnt positions (anything else gets a
+        plain tensor for the rest of the step and is packed by copy as before).
+
+        A request is matched by position and size only, so a step whose nodes run in another order, or skip one, hands a node
+        ANOTHER node's slab.  The invariant that keeps this harmless: a gradient is never read from a place in the flat buffer
+        after something else may have written there.  A slab is served at most once per step and never once its bucket has
+        been flushed (the all-reduce owns that memory then); and before a flush writes into its bucket — pack copies,
+        zero-fill, the collective — it moves out every gradient of a not yet flushed parameter that lives there without
+        owning the place (_flush: on the communication stream, behind the training and the weight-gradient stream)."""
         if self._learning:
+            if not self._rec_cb:  # a backward pass in which none of this reducer's hooks fires is another model's: forget it
+                self._rec_cb = True
+                torch.autograd.Variable._execution_engine.queue_callback(self._end_of_learning_backward)
             t = torch.empty(n, dtype=torch.float32, device=dev)
             self._slab_rec.append((t.data_ptr(), n, t))
             return t
         i, seq = self._slab_i, self._slab_seq
-        if seq is None or i >= len(seq) or seq[i][0] != n:
+        if seq is None or i >= len(seq) or seq[i][0] != n or (seq[i][2] is not None and self._flushed[seq[i][2]]):
             self._slab_i = 1 << 30
             return None
         self._slab_i = i + 1
         at = seq[i][1]
-        return None if at is None else self.flat[at:at + n]
+        if at is None:
+            return None
+        self._served.add(i)
+        return self.flat[at:at + n]
+
+    def _end_of_learning_backward(self):
+        self._rec_cb = False
+        if self._learning and not self._arrival:
+            self._slab_rec = []
 
     def _rearm(self):
         self._slab_i = 0
+        self._served = set()
         self._pending = [0] * len(self.buckets)
         self._flushed = [False] * len(self.buckets)
         self._ready = [False] * len(self.buckets)
@@ -446,13 +484,28 @@ class GradReducer:
         f0, f1 = self.flat.data_ptr(), self.flat.data_ptr() + 4 * self.flat.numel()
         # (a gradient that sits in the flat buffer but not in its own slot — a node served another node's slab — is copied
         #  out first: its place may be another parameter's destination)
-        grads = [ps[i].grad.clone() if f0 <= ps[i].grad.data_ptr() < f1 else ps[i].grad for i in move]
+        grads = [ps[i].grad for i in move]
+        inside = [j for j, g in enumerate(grads) if f0 <= g.data_ptr() < f1]
         self.copied_floats += sum(ps[i].numel() for i in move)
         self.inplace_floats += sum(ps[i].numel() for i in have) - sum(ps[i].numel() for i in move)
         dst = [views[i] for i in move]
         missing = [views[i] for i in range(len(ps)) if ps[i].grad is None] if len(have) < len(ps) else []
+        # evict before overwrite (see _arena): a served slab of this bucket that does not hold its owners' gradients holds
+        # another node's — those of parameters whose own bucket is still to be flushed leave before anything is written here
+        guests = []
+        if self._served and (move or missing):
+            home = set(have).difference(move)
+            if any(k in self._served and not home.issuperset(idx) for k, idx in self._bslabs[b]):
+                b0, b1 = f0 + 4 * lo, f0 + 4 * hi
+                guests = [q for q in self.params if q.grad is not None and not self._flushed[self._slot[q]]
+                          and b0 <= q.grad.data_ptr() < b1]
 
         def pack():
+            for q in guests:
+                q.grad = q.grad.clone()
+                self._keep.append(q.grad)
+            for j in inside:
+                grads[j] = grads[j].clone()
             if missing:  # finish(): gradient-less parameters contribute zeros to the average
                 torch._foreach_zero_(missing)
             if grads and not _DIAG_NO_PACK:
@@ -539,7 +592,7 @@ class GradReducer:
                     slabs = (slabs[0], {self.params[i]: w for i, w in slabs[1].items()})
                 self._layout(hot, [p for p in self.params if p not in hot_set], slabs)
                 if slabs is not None:  # (served by call order and size; a rank whose nodes ask differently gets plain tensors)
-                    self._slab_seq = [(n, self._slab_at.get(k)) for k, n in enumerate(slabs[0])]
+                    self._slab_seq = [(n, self._slab_at.get(k), self._slab_bucket.get(k)) for k, n in enumerate(slabs[0])]
                 self._slab_rec, self._pslab = [], {}
                 self._learning = False
                 if self.sparse_hooks:
@@ -618,8 +671,12 @@ class GradReducer:
 
     def unused_of(self, step_id):
         """Indices (into self.params) of the parameters no rank used in finish() number `step_id`, or None while the host has
-        not seen that step's flags yet (they arrive one step late)."""
-        return self._known.get(step_id)
+        not seen that step's flags yet (they arrive one step late; sooner if their copy happens to be complete — asked with
+        an event query, never waited for)."""
+        un = self._known.get(step_id)
+        if un is None and self._usage_pending is not None and self._usage_pending[2] == step_id and self._usage_pending[1].query():
+            un = self._known[step_id] = {i for i, f in enumerate(self._usage_pending[0].tolist()) if not f}
+        return un
 
     def view_of(self, p):
         """The slice of the flat, rank-averaged buffer that holds p's gradient (zeros when no rank produced one)."""
@@ -630,6 +687,8 @@ class GradReducer:
     used_mask = None       # device int32 [len(params)]: 1 = some rank produced a gradient in the step just finished (exact)
     time_exposed = False   # bench.py: record an event pair around the wait in finish()
     sparse_hooks = True    # one hook per bucket once the arrival order is known (False: a hook on every parameter)
+    arena_on_host = False  # the slab arena for host tensors too (tests: pure-torch stand-ins of the backward nodes ask ops._grad_slab)
+    _rec_cb = False        # learning pass: the end-of-backward callback of _arena is queued
 
     def exposed_comm_ms(self):
         """Mean GPU time per step the backward stream spent waiting in finish() (time_exposed = True), then reset."""
